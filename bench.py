@@ -8,15 +8,18 @@ fp32 head; batch 256 per GPU.  A step = forward + backward + gradient all-reduce
 both towers (nothing frozen, nothing skipped).  Inputs are resident in HBM before the timed region.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given, and
+prints ONE JSON line (rank 0) with the driver's contract fields (`ms_per_step`: milliseconds per timed step) and, at N > 1,
+  comm         : bytes all-gathered / all-reduced per step, device time of the gradient all-reduces and how long the
+                 compute stream waited for them (mmgclip/distributed.py: GradSync.report).
+`--full` adds the measurements that take runs or steps of their own, and the full record of the run (`--detail-out`):
   roofline     : the kernel instantiation with the largest share of a step - algorithmic bytes / FLOPs of every launch over its
                  HIP-event duration, per shape class.  The K timed steps run UNINSTRUMENTED; the events are recorded in
                  `--profile-steps` extra steps after the timed region, with both towers on one stream so that no event pair spans
                  another stream's kernel (mmgclip/profile.py), labelled with the instantiation name rocprofv3 prints;
-  comm         : (N > 1) bytes all-gathered / all-reduced per step, device time of the gradient all-reduces and how long the
-                 compute stream waited for them (mmgclip/distributed.py: GradSync.report);
   cpu_baseline : the CPU oracle (oracle/*, fp32 PyTorch restatement) on BASELINE config C1 (n=8, 224x224) at S=77 and S=256, the
                  reference-faithful step at both lengths and a bounded sample of C2 itself, timed on this host's cores, rank 0,
                  N=1 only.
@@ -126,6 +129,44 @@ def write_detail(detail, path):
             return alt
         except OSError:
             return None
+
+
+DUMP_SAMPLE = 1 << 21      # elements of the parameter / gradient samples that --dump-outputs writes (8 MB each in fp32)
+
+
+def output_arrays(outputs, loss, model, sample=DUMP_SAMPLE, seed=0):
+    """What one training step hands its caller, as float32 numpy arrays: the loss, the two L2-normalised embeddings [n, 512] and the
+    logit scale the loss consumed, and - the step's other product - the parameters after the optimizer update and the gradients it
+    applied.  Those two are a fixed sample: `sample` element positions drawn by a generator seeded with `seed` over the parameters
+    that received a gradient, concatenated in `named_parameters()` order, so that the same run draws the same elements every time."""
+    import numpy as np
+    arrays = {"loss": loss, "image_embeddings": outputs["image_embeddings"], "text_embeddings": outputs["text_embeddings"],
+              "logit_scale": outputs["logit_scale"]}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    params = [p for _, p in model.named_parameters() if p.grad is not None]
+    total = sum(p.numel() for p in params)
+    idx = torch.randint(total, (min(sample, total),), generator=torch.Generator().manual_seed(seed)).unique()    # sorted
+    vals, grads, off = [], [], 0
+    for p in params:
+        lo, hi = torch.searchsorted(idx, torch.tensor([off, off + p.numel()])).tolist()
+        if hi > lo:
+            sel = (idx[lo:hi] - off).to(p.device)
+            vals.append(p.detach().reshape(-1)[sel].float().cpu())
+            grads.append(p.grad.detach().reshape(-1)[sel].float().cpu())
+        off += p.numel()
+    arrays["param_sample"] = torch.cat(vals).numpy() if vals else np.zeros(0, np.float32)
+    arrays["grad_sample"] = torch.cat(grads).numpy() if grads else np.zeros(0, np.float32)
+    return arrays
+
+
+def dump_outputs(arrays, out_dir, limit=64 << 20):
+    """`out_dir/<name>.npy` for every array (float32), at most `limit` bytes in all."""
+    import numpy as np
+    if sum(a.size * 4 for a in arrays.values()) > limit:
+        raise ValueError(f"outputs above {limit} bytes: {({k: a.size * 4 for k, a in arrays.items()})}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def build(args, comm):
@@ -285,22 +326,30 @@ def main():
                          "reference's own step (pre-extracted 768-d features, frozen BERT forward, two trainable projections)")
     ap.add_argument("--checkpoint", action="store_true", help="gradient checkpointing of the image tower (micro-batch granularity)")
     ap.add_argument("--fp8", action="store_true", help="ConvNeXt blocks with C >= 512: forward pointwise GEMMs on e4m3 MFMA (config C5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements after the timed steps: the roofline leg (--profile-steps instrumented steps), the "
+                         "CPU oracle baseline (N = 1) and the full record of the run (--detail-out); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, embeddings, logit scale, a fixed sample of the updated parameters "
+                         "and of their gradients) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline leg")
     ap.add_argument("--one-stream", action="store_true",
                     help="text tower on the caller's stream in EVERY step (what the roofline leg's extra steps always do): the setting the "
                          "rocprofv3 kernel trace under profiles/ is collected with, so that its per-kernel averages are the kernels' own")
     ap.add_argument("--profile-steps", type=int, default=2,
-                    help="instrumented steps run AFTER the timed region for the roofline leg (one stream, HIP events per launch)")
+                    help="(--full) instrumented steps run AFTER the timed region for the roofline leg (one stream, HIP events per launch)")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="file for the full record (every kernel instantiation, every shape class, every CPU leg); stdout carries only the "
-                         "compact contract line (< 4 KB)")
+                    help="(--full) file for the full record (every kernel instantiation, every shape class, every CPU leg); stdout carries "
+                         "only the compact contract line (< 4 KB)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--cpu-baseline-worker", type=float, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker is not None:
         cpu_baseline_worker(args.cpu_baseline_worker)
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.micro_batch is None:
         # measured at C2 (same box): 64 -> 669, 128 -> 685, 256 -> 690 pairs/s (101 / 109 / 126 GiB); ConvNeXt-B at 64 already
         # peaks at 267 GiB
@@ -340,12 +389,13 @@ def main():
     extra = [p for n, p in model.named_parameters() if not (n.startswith("image_encoder.") or n.startswith("text_encoder."))]
     optimizer = None
     sync = None
+    last = {}                                 # the latest step's model outputs (--dump-outputs)
 
     def step():
         nonlocal optimizer, sync
         if optimizer is not None:
             optimizer.zero_grad(set_to_none=True)
-        outputs = model(batch, materialize_logits=False)
+        outputs = last["outputs"] = model(batch, materialize_logits=False)
         loss, _ = criterion(**outputs)
         if sync is None:                      # arenas exist after the first forward
             sync = distributed.GradSync(comm, arenas(), extra, timing=comm is not None)
@@ -385,6 +435,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs and rank == 0:                   # before the roofline leg's extra steps change the parameters
+        dump_outputs(output_arrays(last["outputs"], loss, model), args.dump_outputs)
     comm_block = None
     if comm is not None and sync is not None:
         comm_block = {**sync.report(), **{k + "_per_step": v // max(args.steps, 1) for k, v in comm.report().items()},
@@ -392,7 +444,8 @@ def main():
 
     # the roofline leg: extra steps, every launch of the hot kernels between two HIP events, both towers on ONE stream
     profile_ms = None
-    if not args.no_roofline and args.profile_steps > 0:
+    roofline = args.full and not args.no_roofline and args.profile_steps > 0
+    if roofline:
         model.text_stream_enabled = False
         step()                                            # (one un-recorded step on the one-stream schedule)
         linalg.PROFILE.enable()
@@ -438,7 +491,7 @@ def main():
                    "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)},
     }
     if rank == 0:
-        if not args.no_roofline and args.profile_steps > 0:
+        if roofline:
             kernels = linalg.PROFILE.kernels()
             # HBM bytes per launch from the rocprofv3 PMC passes of this same command (tools/collect_traffic.sh; the
             # counters cannot be read from inside the process), corrected as MI355X_MICROARCH.md prescribes
@@ -476,11 +529,13 @@ def main():
                             "on the main stream; names are the dispatcher's instantiations as rocprofv3 prints them"}
         if comm_block is not None:
             out["comm"] = comm_block
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-        where = write_detail(out, args.detail_out)
-        if where and where.startswith(ROOT + os.sep):
-            where = os.path.relpath(where, ROOT)
+        where = None
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline()
+            where = write_detail(out, args.detail_out)
+            if where and where.startswith(ROOT + os.sep):
+                where = os.path.relpath(where, ROOT)
         print(contract_line(out, where), flush=True)
     if comm is not None:
         dist.barrier()

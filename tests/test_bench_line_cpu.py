@@ -75,3 +75,39 @@ def test_detail_file_round_trips(tmp_path, recorded):
     import bench
     p = bench.write_detail(recorded, str(tmp_path / "sub" / "bench_detail.json"))
     assert p and json.load(open(p)) == recorded
+
+
+def test_output_arrays_are_the_step_outputs_and_a_fixed_parameter_sample(tmp_path):
+    """--dump-outputs: the loss, the embeddings and the logit scale as float32, and the same seeded sample of the parameters and their
+    gradients (positions over the parameters in named_parameters() order) every time."""
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 32), torch.nn.Linear(32, 16))
+    frozen = torch.nn.Parameter(torch.ones(5))               # no gradient: not part of the sample
+    model.register_parameter("frozen", frozen)
+    emb = torch.nn.functional.normalize(model(torch.randn(8, 64)), dim=1)
+    loss = (emb[:, :8] * emb[:, 8:]).sum()
+    loss.backward()
+    outputs = {"image_embeddings": emb, "text_embeddings": emb.flip(0), "logit_scale": torch.tensor(2.6593).exp()}
+    a = bench.output_arrays(outputs, loss, model, sample=500)
+    b = bench.output_arrays(outputs, loss, model, sample=500)
+    assert set(a) == {"loss", "image_embeddings", "text_embeddings", "logit_scale", "param_sample", "grad_sample"}
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert a["loss"] == np.float32(loss.item()) and a["image_embeddings"].shape == (8, 16)
+    params = [p for n, p in model.named_parameters() if n != "frozen"]
+    idx = torch.randint(sum(p.numel() for p in params), (500,), generator=torch.Generator().manual_seed(0)).unique()
+    assert 400 < len(idx) == len(a["param_sample"]) == len(a["grad_sample"])
+    assert np.array_equal(a["param_sample"], torch.cat([p.detach().reshape(-1) for p in params])[idx].numpy())
+    assert np.array_equal(a["grad_sample"], torch.cat([p.grad.reshape(-1) for p in params])[idx].numpy())
+    assert not np.array_equal(a["param_sample"], bench.output_arrays(outputs, loss, model, sample=500, seed=1)["param_sample"])
+
+    bench.dump_outputs(a, str(tmp_path / "out"))
+    for k, v in a.items():
+        got = np.load(str(tmp_path / "out" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, v), k
+    with pytest.raises(ValueError):
+        bench.dump_outputs({"big": np.zeros(1 << 20, np.float32)}, str(tmp_path / "big"), limit=1 << 20)
+    assert not os.path.exists(str(tmp_path / "big"))

@@ -180,6 +180,7 @@ def _experiment_worker(rank, world, port, tmpdir, global_loss, q):
             sys.path.insert(0, p)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(1)
+    torch.cuda.is_available = lambda: False           # the experiment stays on the host on a GPU machine too (this worker process only)
     from mmgclip import distributed, head
     head._HipHeadBackend = OracleHeadBackend          # this worker process only
     comm = distributed.init_from_env("gloo")
@@ -215,6 +216,7 @@ def test_classifier_experiment_train_syncs_gradients_gloo(tmp_path, global_loss,
             sys.path.insert(0, p)
     from mmgclip import head
     monkeypatch.setattr(head, "_HipHeadBackend", OracleHeadBackend)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)          # on the host, as the two ranks ran
     exp, l_ref = _run_experiment(None, 0, 1, str(tmp_path))
     ref = {k: v.detach().numpy() for k, v in exp.model.state_dict().items()}
     moved = max(float(np.abs(ref[k] - v.detach().numpy()).max()) for k, v in _TinyClip().state_dict().items())

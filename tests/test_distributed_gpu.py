@@ -243,7 +243,7 @@ def test_bench_two_ranks_prints_one_compact_line_with_comm(dev, tmp_path):
     detail = str(tmp_path / "bench_detail.json")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--image-size", "224", "--micro-batch", "8", "--backend", "gloo", "--profile-steps", "1", "--detail-out", detail]
+           "--image-size", "224", "--micro-batch", "8", "--backend", "gloo", "--full", "--profile-steps", "1", "--detail-out", detail]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

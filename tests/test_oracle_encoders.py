@@ -266,6 +266,20 @@ def test_c1_step_oracle_matches_third_party_and_reference_golden(golden_dir, S):
     keys = [k[5:] for k in g.files if k.startswith("grad.") and not k.endswith(".rows")]
     assert len(keys) > 100
     for k in keys:
+        if k.endswith("attention.self.key.bias"):
+            # softmax is invariant to a shift of all keys: the exact gradient is 0 and both sides hold only fp32 rounding noise
+            # (<= 2e-7 of the same layer's value-bias gradient), which differs from one host CPU to the next; its size is checked
+            vb = np.abs(g["grad." + k.replace("key.bias", "value.bias")]).max()
+            assert np.abs(params[k].grad.numpy()).max() <= 1e-5 * vb and np.abs(g["grad." + k]).max() <= 1e-5 * vb, k
+            continue
+        if k.endswith("attention.self.query.bias"):
+            # small by construction in the last layers (only the [SEP] row feeds the loss: 2e-4 of the value bias's in layer 11),
+            # a difference of large terms whose fp32 rounding (1e-7 ... 3e-7 of the value bias's, host CPU dependent) is measured
+            # against the larger of its own size and 1 % of the layer's value-bias gradient
+            vb = np.abs(g["grad." + k.replace("query.bias", "value.bias")]).max()
+            err = np.abs(params[k].grad.numpy().astype(np.float64) - g["grad." + k]).max() / max(np.abs(g["grad." + k]).max(), 1e-2 * vb)
+            assert err <= 5e-4, f"{k}: max error {err:.3e}"
+            continue
         _close(params[k].grad, g["grad." + k], 5e-4, k)
     rows = torch.from_numpy(g["word_rows"])
     _close(params["text.embeddings.word_embeddings.weight"].grad[rows], g["grad.text.embeddings.word_embeddings.weight.rows"], 5e-4, "word rows")

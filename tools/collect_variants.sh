@@ -14,7 +14,7 @@ run() {
     local log="$OUT.$N.log" line rc
     echo "# bench.py $*" >&2
     # ENVV="NAME=value ..." in front of a run line sets knobs for that line only (recorded in its flags)
-    env $ENVV timeout -k 10 280 python3 "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --detail-out "$OUT.$N.detail.json" "$@" > "$log.out" 2> "$log"
+    env $ENVV timeout -k 10 280 python3 "$REPO/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline --detail-out "$OUT.$N.detail.json" "$@" > "$log.out" 2> "$log"
     rc=$?
     line=$(grep '^{' "$log.out" | tail -1)
     if [ "$rc" -ne 0 ] || [ -z "$line" ]; then
