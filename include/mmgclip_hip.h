@@ -133,7 +133,9 @@ int mmg_layernorm_bwd_f32(const void* dy, int lddy, const float* x, int ldx, con
                           const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C,
                           const void* add, int ldadd, mmg_stream_t stream);
 /* dx (bf16) and dgamma/dbeta (fp32, ACCUMULATED; both NULL to skip) given dy in the layout the forward wrote;
- * add (bf16 [M,C], nullable) is added to dx: the residual-path gradient of pre-LN transformer blocks. */
+ * add (bf16 [M,C], nullable) is added to dx: the residual-path gradient of pre-LN transformer blocks.
+ * patch != 0 with odd H and / or W (H, W > 1): dy is [(M / (H W)) (H/2) (W/2), 4C] (integer division), as mmg_layernorm_fwd wrote
+ * it; the pixels of the dropped last row / column read nothing of dy, get dx = 0 (or add's row) and add nothing to dgamma / dbeta. */
 int mmg_layernorm_bwd(const void* dy, int lddy, const void* x, int ldx, const float* mean, const float* rstd,
                       const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C, int patch,
                       int H, int W, const void* add, int ldadd, mmg_stream_t stream);

@@ -16,7 +16,10 @@
 // (G = power of two >= C/8, <= 64), 64/G rows per wave, CH 16-byte chunks per lane.
 // `patch` != 0 : the normalised row m = (n,h,w) is written to (read from, in the backward) the 2x2-patchified
 // position  row (n, h/2, w/2), columns ((h&1)*2 + (w&1))*C ..  of a [M/4, 4C] matrix, so that the following
-// 2x2 stride-2 convolution is a plain GEMM (ConvNeXt downsample layers).
+// 2x2 stride-2 convolution is a plain GEMM (ConvNeXt downsample layers).  Odd H / W follow torch's floor rule in both
+// directions: the matrix has (M / (H W)) * (H/2) * (W/2) rows, the pixels of the last row / column have no position in it -
+// the forward writes nothing for them, the backward reads no dy for them (its load is clamped to row 0 and zero is selected),
+// gives them dx = 0 (+ `add`) and keeps them out of dgamma / dbeta; their lanes still take part in every shuffle and barrier.
 // ---------------------------------------------------------------------------------------------
 struct LNArgs {
     const bf16_t* x; int ldx;
@@ -170,7 +173,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const LNArgs a) {
 
     for (int m = blockIdx.x * rows_per_block + wave * RPW + gr; m < a.M; m += gridDim.x * rows_per_block) {
         const float mu = a.mean[m], rs = a.rstd[m];
-        const size_t gbase = ln_out_offset(a, m, a.lddy);
+        // a pixel of the dropped last row / column has no dy: its load goes to a valid address (row 0) and zero is selected afterwards, so
+        // its lanes stay in the group sums with a zero contribution, dx = 0 (+ add), nothing reaches dgamma / dbeta
+        const size_t goff = ln_out_offset(a, m, a.lddy);
+        const bool live = goff != (size_t)-1;
+        const size_t gbase = live ? goff : 0;
         float xh[CH][8], g[CH][8];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -179,7 +186,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const LNArgs a) {
             if (c < nchunks) {
                 float xv[8], dyv[8];
                 ln_load_x8(a, m, c, xv);
-                unpack8(*reinterpret_cast<const uint4*>(a.dy + gbase + c * 8), dyv);
+                const uint4 dr = *reinterpret_cast<const uint4*>(a.dy + gbase + c * 8);
+                unpack8(live ? dr : make_uint4(0u, 0u, 0u, 0u), dyv);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     xh[k][e] = (xv[e] - mu) * rs;
@@ -310,13 +318,19 @@ __global__ __launch_bounds__(256) void layernorm_bwd_plain_kernel(const LNArgs a
     const float inv_c = 1.0f / (float)a.C;
     const int rows_per_block = 4 * RPW;
     for (int m = blockIdx.x * rows_per_block + wave * RPW + gr; m < a.M; m += gridDim.x * rows_per_block) {
-        const size_t gbase = ln_out_offset(a, m, a.lddy);
+        // dropped last row / column of an odd map (see layernorm_bwd_kernel): load from a valid address, then select zero
+        const size_t goff = ln_out_offset(a, m, a.lddy);
+        const bool live = goff != (size_t)-1;
+        const size_t gbase = live ? goff : 0;
         uint4 xr[CH], dr[CH];
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
             xr[k] = *reinterpret_cast<const uint4*>(a.x + (size_t)m * a.ldx + (gl + k * G) * 8);
             dr[k] = *reinterpret_cast<const uint4*>(a.dy + gbase + (gl + k * G) * 8);
         }
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+            if (!live) dr[k] = make_uint4(0u, 0u, 0u, 0u);
         const float mu = a.mean[m], rs = a.rstd[m];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -494,9 +508,9 @@ MMG_API int mmg_layernorm_bwd(const void* dy, int lddy, const void* x, int ldx, 
                               const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C,
                               int patch, int H, int W, const void* add, int ldadd, hipStream_t stream) {
     if (ln_check("mmg_layernorm_bwd", M, C, patch, H, W)) return 1;
-    MMG_CHECK_ARG(!patch || (H % 2 == 0 && W % 2 == 0), "mmg_layernorm_bwd: training through the patchified layout needs even H=%d W=%d", H, W);
+    // odd H / W: dy is [(M / (H W)) (H/2) (W/2), 4C] as the forward wrote it; the dropped pixels get dx = 0 (+ add) and no dy address is formed
     MMG_CHECK_ARG(dy && x && mean && rstd && gamma && dx && ((dgamma == nullptr) == (dbeta == nullptr)) &&
-                      ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C && lddx >= C,
+                      ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C && lddx >= C && lddy >= (patch ? 4 * C : C),
                   "mmg_layernorm_bwd: bad pointer or leading dimension");
     LNArgs a = {};
     a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);

@@ -2,7 +2,7 @@
 with the collate_fn's keys and dtypes (dataset.py:343-351 / :548-561) from seeded generators.
 
     image_features  fp32 [n,1,768,1,1]  |N(1, 0.4)|   (pre-extracted mode)        or
-    image           fp32 [n,Cin,H,W]    U[0,1)        (pixel encoders)
+    image           fp32 [n,Cin,H,W]    U[0,1)        (pixel encoders; image_size = an int for square images or an (H, W) pair)
     text_tokens     {input_ids, token_type_ids, attention_mask} int64 [n,S]: [CLS]=101 ... [SEP]=102, body U{1000..V-1},
                     pad 0, lengths U{8..S}
     image_label     int64 [n,1], image_id list[str], image_description list[str], prompt_labels list[dict]
@@ -31,13 +31,23 @@ def synthetic_tokens(n, S, vocab_size=28996, generator=None, fixed_length=None):
     return TokenBatch(input_ids=ids, token_type_ids=torch.zeros(n, S, dtype=torch.long), attention_mask=mask)
 
 
+def image_hw(image_size):
+    """int -> (size, size); an (H, W) pair (tuple or list, as a config file or an override spells it) -> (H, W)."""
+    if isinstance(image_size, (list, tuple)):
+        if len(image_size) != 2:
+            raise ValueError(f"image_size must be an int or an (H, W) pair, got {image_size!r}")
+        return int(image_size[0]), int(image_size[1])
+    return int(image_size), int(image_size)
+
+
 def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab_size=28996, seed=42, with_impression=False):
     g = torch.Generator().manual_seed(seed)
     batch = {}
     if image_size is None:
         batch["image_features"] = (1.0 + 0.4 * torch.randn(n, 1, feature_dim, 1, 1, generator=g)).abs()
     else:
-        batch["image"] = torch.rand(n, in_chans, image_size, image_size, generator=g)
+        H, W = image_hw(image_size)
+        batch["image"] = torch.rand(n, in_chans, H, W, generator=g)
     batch["text_tokens"] = synthetic_tokens(n, S, vocab_size, g)
     if with_impression:
         batch["image_impression_tokens"] = synthetic_tokens(n, S, vocab_size, g)

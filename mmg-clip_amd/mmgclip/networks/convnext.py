@@ -17,6 +17,11 @@ rows (the LayerNorm kernel writes the patchified layout directly).  Blocks with 
 Linear + layer scale + residual as one fused launch (csrc/cnblock_mlp.hip); for C <= 192 the backward recomputes the hidden
 row on chip.  Saved for backward per block and pixel: block input (C), depthwise output (C) and - only where the backward
 does not recompute it - the pre-GELU hidden (4C) in bf16 + LN statistics; LN output and GELU output are rebuilt.
+
+Image sizes: any H, W >= 32, forward and backward.  Every strided layer floors (stem H // 4, downsample // 2) and drops the odd last row /
+column as torch's convolutions do; the forward records each stage's map size and the backward reads it back (dropped pixels get a zero
+gradient from mmg_layernorm_bwd).  `forward` also takes a list of [Cin, H_i, W_i] images of different sizes: grouped by size in order of first
+appearance (`group_by_size`), each group in micro-batches of its own, features and gradients routed back in input order.
 """
 import os
 
@@ -192,26 +197,25 @@ class ConvNextTower(nn.Module):
                 wc[f"ds{si}.wt"] = K.transpose_cast_bf16(wds)
         self._wc, self._wc_version = wc, v
 
-    def _decide_save_ln(self, n_alive, H, W, device, ckpt=False):
+    def _decide_save_ln(self, n_alive, H, W, device, ckpt=False, more=()):
         """n_alive = images whose saved tensors are alive at once (the whole batch; one micro-batch under checkpointing).
+        more: further (n_alive, H, W) triples alive at the same time (a batch of several image sizes).
         ckpt: under checkpointing the saved tensors of ONE micro-batch are all the activation memory there is, so the optional copies may take a
         larger share of the device (round 4, ConvNeXt-B in micro-batches of 128: 264 against 249 pairs/s with them, peak 238 GiB)."""
-        extra, hh, ww = 0, H // 4, W // 4
-        for si in range(4):
-            C = self.dims[si]
-            if not (K.cnblock_supported(C) and K.cnblock_bwd_mode(C) == 1) and not (K.cnblock_bwd_mode(C) == 2 and self.fused_bwd_saved_h):
-                extra += self.depths[si] * n_alive * hh * ww * C * 2
-            hh, ww = hh // 2, ww // 2
+        extra, keep8 = 0, 0
+        for n_alive, H, W in ((n_alive, H, W),) + tuple(more):
+            hh, ww = H // 4, W // 4
+            for si in range(4):
+                C = self.dims[si]
+                if not (K.cnblock_supported(C) and K.cnblock_bwd_mode(C) == 1) and not (K.cnblock_bwd_mode(C) == 2 and self.fused_bwd_saved_h):
+                    extra += self.depths[si] * n_alive * hh * ww * C * 2
+                if self.fp8 and self.fp8_bwd and C % 128 == 0 and C >= self.fp8_min_channels:
+                    keep8 += self.depths[si] * n_alive * hh * ww * C * 5
+                hh, ww = hh // 2, ww // 2
         total = torch.cuda.get_device_properties(device).total_memory
         # 8-bit backward: its forward keeps the e4m3 LayerNorm output and activation (5 C bytes per row and block on top of the bf16 side output)
         # - only while that stays below 15 % of the device memory (C5, checkpointed micro-batches of 64: 23 GB, on; ConvNeXt-B at 256 images
         # without checkpointing: 93 GB on top of 267 GiB, off - that forward then saves what rounds 1 - 3 saved and its backward runs in bf16)
-        keep8, hh, ww = 0, H // 4, W // 4
-        for si in range(4):
-            C = self.dims[si]
-            if self.fp8 and self.fp8_bwd and C % 128 == 0 and C >= self.fp8_min_channels:
-                keep8 += self.depths[si] * n_alive * hh * ww * C * 5
-            hh, ww = hh // 2, ww // 2
         mode8 = os.environ.get("MMG_FP8_BWD", "auto")
         self.fp8_bwd_now = self.fp8 and self.fp8_bwd and (mode8 == "1" or keep8 <= (0.20 if ckpt else 0.15) * total)
         if self.save_ln_mode in ("0", "1"):
@@ -229,7 +233,7 @@ class ConvNextTower(nn.Module):
         f, wc = self.model.features, self._wc
         n, _, H, W = img.shape
         h, w_ = H // 4, W // 4
-        saved = {}
+        saved = {"maps": [(h, w_)]}                 # map size per stage: floored at every stride, so the backward reads them back
         p0 = K.patchify(img, 4, self.kp, self.scale16)
         s0 = L.gemm_nt(p0, wc["stem.w"], bias=f[0][0].bias.data)
         x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
@@ -296,6 +300,7 @@ class ConvNextTower(nn.Module):
                     saved[f"ds{si}"] = (x, mean, rstd, ld)
                 x = xn
                 h, w_ = h // 2, w_ // 2
+                saved["maps"].append((h, w_))
         feat = K.avgpool_fwd(x, n, h * w_, self.dims[-1])
         saved["shape"] = (n, H, W)
         return feat, saved
@@ -307,7 +312,8 @@ class ConvNextTower(nn.Module):
         feature maps are still in backward."""
         f, wc, A = self.model.features, self._wc, self._arena
         n, H, W = saved["shape"]
-        h, w_ = H // 32, W // 32
+        maps = saved["maps"]
+        h, w_ = maps[3]
         gname = lambda mod, leaf: A.g(self._pname[id(mod)] + "." + leaf)      # noqa: E731
         dx = K.avgpool_bwd(dfeat, n, h * w_, self.dims[-1])
         for si in range(3, -1, -1):
@@ -317,7 +323,7 @@ class ConvNextTower(nn.Module):
                 conv, lnm = f[2 + 2 * si][1], f[2 + 2 * si][0]
                 L.gemm_tn_acc(dx, ld, tmp[f"ds{si}.dw"], colsum=gname(conv, "bias"))
                 dld = L.gemm_nt(dx, wc[f"ds{si}.wt"])
-                h, w_ = h * 2, w_ * 2
+                h, w_ = maps[si]                   # (odd sizes: the dropped last row / column gets a zero gradient here)
                 dx = K.layernorm_bwd(dld, x, mean, rstd, lnm.weight.data, gname(lnm, "weight"), gname(lnm, "bias"),
                                      patch_hw=(h, w_))
                 del dld
@@ -443,41 +449,92 @@ class ConvNextTower(nn.Module):
         return h, w
 
     def forward(self, images):
-        _hip.require_gpu(images)
-        if images.shape[-2] < 32 or images.shape[-1] < 32:
-            raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(images.shape)}")
-        self._materialize(images.device)
+        """images: fp32 [n, Cin, H, W] (any H, W >= 32), or a list / tuple of [Cin, H_i, W_i] tensors whose sizes may differ: those are grouped by
+        size (`group_by_size`), every group runs in micro-batches of its own, and row i of the result belongs to images[i]."""
+        plan = None
+        if isinstance(images, (list, tuple)):
+            if not images or any(not torch.is_tensor(t) or t.dim() != 3 for t in images):
+                raise ValueError("a list of images must hold [Cin, H, W] tensors")
+            for t in images:
+                _hip.require_gpu(t)
+                if t.shape[-2] < 32 or t.shape[-1] < 32:
+                    raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(t.shape)}")
+            plan = group_by_size([tuple(t.shape[-2:]) for t in images], self.micro_batch)
+            device = images[0].device
+        else:
+            _hip.require_gpu(images)
+            if images.shape[-2] < 32 or images.shape[-1] < 32:
+                raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(images.shape)}")
+            device = images.device
+        self._materialize(device)
         self._pname = {id(m): "features." + n for n, m in self.model.features.named_modules()}
         needs_grad = torch.is_grad_enabled() and self._arena.any_trainable()
-        if needs_grad and (images.shape[-2] % 32 or images.shape[-1] % 32):
-            raise NotImplementedError("training the ConvNeXt tower needs H and W to be multiples of 32 (inference accepts any "
-                                      "size >= 32: strided layers drop the remainder exactly as torch's convolutions do)")
         note_forward(self, needs_grad)
-        return _ConvNextFn.apply(self, images.float().contiguous(), stream_anchor(self, self._anchor.device) if needs_grad else None)
+        anchor = stream_anchor(self, self._anchor.device) if needs_grad else None
+        if plan is None:
+            return _ConvNextFn.apply(self, images.float().contiguous(), anchor, None)
+        return _ConvNextFn.apply(self, [t.float() for t in images], anchor, plan)
+
+
+def group_by_size(sizes, micro_batch):
+    """sizes: one (H, W) per image -> (micro_batches, inverse).  Images of one size form a group; groups come in the order in which their size
+    first appears, the images inside a group in input order, and every group is cut into micro-batches of at most `micro_batch` images
+    (lists of input indices).  Concatenating the micro-batches gives the processing order; inverse[i] is the position of image i in it, so
+    `processed[inverse]` is in input order."""
+    if micro_batch < 1:
+        raise ValueError(f"micro_batch must be positive, got {micro_batch}")
+    groups = {}
+    for i, hw in enumerate(sizes):
+        groups.setdefault(tuple(int(v) for v in hw), []).append(i)          # (dicts keep insertion order: first appearance)
+    mbs = [idx[k:k + micro_batch] for idx in groups.values() for k in range(0, len(idx), micro_batch)]
+    inverse = [0] * len(sizes)
+    for pos, i in enumerate(j for mb in mbs for j in mb):
+        inverse[i] = pos
+    return mbs, inverse
 
 
 class _ConvNextFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tower, images, anchor):
+    def forward(ctx, tower, images, anchor, plan):
         tower._refresh_working_copies()
         save = anchor is not None
         feats, saved = [], []
         mb = tower.micro_batch
         ckpt = save and tower.checkpoint
+        if plan is None:
+            count, device = images.shape[0], images.device
+            parts = [(lambda i=i: images[i:i + mb]) for i in range(0, count, mb)]
+            alive = [(min(mb, count) if ckpt else count, images.shape[-2], images.shape[-1])]
+        else:                               # images of several sizes: one [k, Cin, H, W] tensor per group-micro-batch, built when it is needed
+            count, device = len(images), images[0].device
+            parts = [(lambda idx=idx: torch.stack([images[j] for j in idx]).contiguous()) for idx in plan[0]]
+            by_size = {}
+            for idx in plan[0]:
+                hw = tuple(images[idx[0]].shape[-2:])
+                by_size[hw] = max(by_size.get(hw, 0), len(idx)) if ckpt else by_size.get(hw, 0) + len(idx)
+            alive = [(k, hw[0], hw[1]) for hw, k in by_size.items()]
+            if ckpt:                        # one micro-batch alive at a time: the largest one decides
+                alive = [max(alive, key=lambda a: a[0] * a[1] * a[2])]
         if save:
-            tower.save_ln = tower._decide_save_ln(min(mb, images.shape[0]) if ckpt else images.shape[0], images.shape[-2], images.shape[-1],
-                                                  images.device, ckpt=ckpt and mb < images.shape[0])
-        for i in range(0, images.shape[0], mb):
+            tower.save_ln = tower._decide_save_ln(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
+        for k, part in enumerate(parts):
             # gradient checkpointing at micro-batch granularity: keep only the pixels, re-run the micro-batch's forward (with its
             # activations saved) right before its backward - activation memory becomes one micro-batch instead of the whole batch.
             # The LAST micro-batch keeps its activations (round 4): the backward starts with it (reverse order), so still only one
             # micro-batch's activations are alive at any time, and one of the n recomputations is not run (MMG_CKPT_KEEP_LAST=0: all are).
-            keep = ckpt and i + mb >= images.shape[0] and os.environ.get("MMG_CKPT_KEEP_LAST", "1") != "0"
-            ft, sv = tower._forward_mb(images[i:i + mb], save and (not ckpt or keep))
+            keep = ckpt and k == len(parts) - 1 and os.environ.get("MMG_CKPT_KEEP_LAST", "1") != "0"
+            pix = part()
+            ft, sv = tower._forward_mb(pix, save and (not ckpt or keep))
             feats.append(ft)
-            saved.append({"recompute": images[i:i + mb]} if (ckpt and not keep) else sv)
+            saved.append({"recompute": part, "n": pix.shape[0]} if (ckpt and not keep) else sv)     # (the pixels are sliced / stacked again then)
+            del pix
         ctx.tower, ctx.saved_mb, ctx.reverse = tower, saved if save else None, ckpt
-        return torch.cat(feats, 0) if len(feats) > 1 else feats[0]
+        ctx.inverse = None
+        out = torch.cat(feats, 0) if len(feats) > 1 else feats[0]
+        if plan is not None and plan[1] != list(range(count)):
+            ctx.inverse = torch.tensor(plan[1], device=device)
+            out = out.index_select(0, ctx.inverse)             # processing order -> input order
+        return out
 
     @staticmethod
     def backward(ctx, dfeat):
@@ -485,7 +542,9 @@ class _ConvNextFn(torch.autograd.Function):
         tower._arena.prepare_grads()
         tmp = tower._alloc_tmp(dfeat.device)
         dfeat = dfeat.float().contiguous()
-        sizes = [sv["recompute"].shape[0] if "recompute" in sv else sv["shape"][0] for sv in ctx.saved_mb]
+        if ctx.inverse is not None:                                # input order -> processing order
+            dfeat = torch.empty_like(dfeat).index_copy_(0, ctx.inverse, dfeat)
+        sizes = [sv["n"] if "recompute" in sv else sv["shape"][0] for sv in ctx.saved_mb]
         starts = [sum(sizes[:k]) for k in range(len(sizes))]
         order = list(range(len(sizes)))
         if ctx.reverse:                      # checkpointing: the micro-batch whose activations were kept (the last one) first
@@ -493,7 +552,7 @@ class _ConvNextFn(torch.autograd.Function):
         for pos, k in enumerate(order):
             sv = ctx.saved_mb[k]
             if "recompute" in sv:
-                _, sv = tower._forward_mb(sv["recompute"], True)
+                _, sv = tower._forward_mb(sv["recompute"](), True)
             i, n = starts[k], sizes[k]
             final = pos == len(order) - 1
             tower._backward_mb(dfeat[i:i + n].contiguous(), sv, tmp, final=final, announce=final and last_backward(tower))
@@ -501,4 +560,4 @@ class _ConvNextFn(torch.autograd.Function):
             ctx.saved_mb[k] = None
         ctx.saved_mb = None
         backward_finished(tower)
-        return None, None, None
+        return None, None, None, None

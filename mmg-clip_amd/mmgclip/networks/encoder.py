@@ -7,7 +7,8 @@ HIP towers (convnext.py / bert.py).
                      and raises on construction.
   BertEncoder       HF-layout BERT; `forward(x: mapping) -> last_hidden_state [B,S,H]`; frozen by default as in the
                     reference (encoder.py:141-142).
-New in-graph image encoders (SURVEY.md §7 decision 1): ConvNextTinyEncoder, ConvNextBaseEncoder — take pixels.
+New in-graph image encoders (SURVEY.md §7 decision 1): ConvNextTinyEncoder, ConvNextBaseEncoder — take pixels: one [n,Cin,H,W]
+tensor of any H, W >= 32, or a list of [Cin,H_i,W_i] images of different sizes (convnext.py); ViTB16Encoder and ResNet50Encoder reject a list.
 """
 import json
 import os
@@ -33,7 +34,8 @@ def _load_state_file(path):
 
 
 class ConvNextTiny(nn.Module):
-    """`model = None` until `from_pretrained(path)`; `forward(x[B,C,H,W]) -> [B,768,1,1]` (features -> avgpool)."""
+    """`model = None` until `from_pretrained(path)`; `forward(x[B,C,H,W]) -> [B,768,1,1]` (features -> avgpool).  Every image runs at its native
+    size, as the reference's feature extractor does: x may also be a list of [C,H_i,W_i] tensors of different sizes."""
 
     def __init__(self):
         super().__init__()
@@ -55,7 +57,7 @@ class ConvNextTiny(nn.Module):
     def forward(self, x):
         if self.model is None:
             raise ImportError("Model was not loaded correctly. Call `from_pretrained` and pass the model file path first.")
-        return self._tower(x).reshape(x.shape[0], -1, 1, 1)
+        return self._tower(x).reshape(len(x), -1, 1, 1)         # (x may be a list of [C,H_i,W_i] images of different sizes)
 
 
 class ResNet50Encoder(ResNetTower):
@@ -75,6 +77,11 @@ class ResNet50Encoder(ResNetTower):
             self.model.load_state_dict(sd, strict=True)
         elif pretrained:
             logger.info("no local ResNet-50 weights (MMGCLIP_RESNET50_WEIGHTS): random initialisation")
+
+    def forward(self, x):
+        if isinstance(x, (list, tuple)):
+            raise ValueError("ResNet50Encoder takes one tensor, not a list of images")
+        return super().forward(x)
 
 
 class _ConvNextEncoder(ConvNextTower):
@@ -121,6 +128,12 @@ class ViTB16Encoder(ViTTower):
             for p in self.parameters():
                 p.requires_grad = False
         logger.info("Initializing 'ViTB16Encoder' as the image encoder.")
+
+    def forward(self, images):
+        if isinstance(images, (list, tuple)):
+            raise ValueError(f"ViTB16Encoder takes one [n, Cin, {self.image_size}, {self.image_size}] tensor (learned positions fix the size), "
+                             "not a list of images")
+        return super().forward(images)
 
 
 class BertEncoder(BertTower):

@@ -102,10 +102,12 @@ class MMGCLIP(nn.Module):
 
     def encode_images(self, batch):
         """[n,1,F,1,1] pre-extracted features -> [n,F] (mmgclip_model.py:76-93); pixel encoders take `batch['image']`
-        (or a 4-D `image_features`) and run the ConvNeXt tower."""
+        (or a 4-D `image_features`) and run the ConvNeXt tower; `batch['image']` may be a list of [Cin,H_i,W_i] tensors of different sizes."""
         name = self.config.networks.image_encoder.name
         if name in PIXEL_ENCODERS:
             pix = batch["image"] if "image" in batch else batch["image_features"]
+            if isinstance(pix, (list, tuple)):      # images of different sizes (ConvNeXt towers): [Cin, H_i, W_i] each
+                return self.image_encoder([p.to(self.device) for p in pix])
             return self.image_encoder(pix.to(self.device))
         flattened_embeddings = torch.flatten(batch['image_features'].to(self.device), 1)
         if name == "ResNet50Encoder":

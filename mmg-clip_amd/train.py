@@ -31,7 +31,8 @@ def build_loaders(cfg, rank=0):
     pixels = cfg.networks.image_encoder.name in PIXEL_ENCODERS
     kw = dict(S=cfg.tokenizer.config.sequence_length, with_impression=cfg.loss.config.loss_name == "MMGCLIPLoss")
     if pixels:
-        kw.update(image_size=_get(cfg, "networks.image_encoder.image_size", 224), in_chans=_get(cfg, "networks.image_encoder.in_chans", 1))
+        size = _get(cfg, "networks.image_encoder.image_size", 224)           # an int, or [H, W] for rectangular images
+        kw.update(image_size=tuple(size) if isinstance(size, (list, tuple)) else size, in_chans=_get(cfg, "networks.image_encoder.in_chans", 1))
     else:
         kw.update(feature_dim=cfg.networks.image_encoder.image_features_dimension)
     bt, bv = cfg.dataloader.train.batch_size, cfg.dataloader.valid.batch_size
