@@ -156,6 +156,20 @@ int mmg_transpose_cast_bf16(const float* src, int R, int C, const float* rowscal
 int mmg_avgpool_fwd(const void* x, float* y, int n, int HW, int C, mmg_stream_t stream);
 int mmg_avgpool_bwd(const float* dy, void* dx, int n, int HW, int C, mmg_stream_t stream);
 
+/* Pooling the views of an exam inside the training graph: feat fp32 [V,C] (views of one study adjacent, studies in batch order) ->
+ * out fp32 [S,C].  Replaces the offline torch.stack(features).mean(0) / .max(0)[0] of StudyFeatureExtractor,
+ * mmgclip/networks/image_features.py:225-245.  offsets: device int32 [S+1], non-decreasing, offsets[0] = 0, offsets[S] = V; study s owns
+ * rows offsets[s] .. offsets[s+1]-1, at least one.  C % 4 == 0, 8 <= C <= 3072.
+ * mode 0 = mean: the rows summed in view order in fp32, one IEEE division by the count; argmax is not touched (nullable).
+ * mode 1 = max: argmax int32 [S,C] receives the winner's row index into feat; the lowest row wins a tie; a NaN in any view gives NaN and
+ *          its row (as torch.max).
+ * Additive entry points: they came without an ABI version step (mmg_abi_version() stays 5). */
+int mmg_view_pool_fwd(const float* feat, const int* offsets, float* out, int* argmax, int S, int C, int mode, mmg_stream_t stream);
+/* dfeat fp32 [V,C]: mode 0: dout[s,c] / count for every view of s; mode 1: dout[s,c] where argmax[s,c] == v, else 0.  Like the forward it
+ * writes every element exactly once (no atomics, no memset): bit-reproducible. */
+int mmg_view_pool_bwd(const float* dout, const int* offsets, const int* argmax, float* dfeat, int S, int V, int C, int mode,
+                      mmg_stream_t stream);
+
 /* Stem im2col: fp32 pixels [n,Cin,H,W] -> bf16 rows (n,h/P,w/P) x (kh,kw,cin), zero-padded to Kp columns;
  * scale16 != 0 applies ((65535 x) - 32767.5)/32767.5 (mmgclip/networks/image_features.py:95-99).  H, W need not be
  * multiples of P: the remainder rows / columns are ignored, as a stride-P convolution does. */

@@ -6,6 +6,9 @@ with the collate_fn's keys and dtypes (dataset.py:343-351 / :548-561) from seede
     text_tokens     {input_ids, token_type_ids, attention_mask} int64 [n,S]: [CLS]=101 ... [SEP]=102, body U{1000..V-1},
                     pad 0, lengths U{8..S}
     image_label     int64 [n,1], image_id list[str], image_description list[str], prompt_labels list[dict]
+
+Exams (`views_per_study=(lo, hi)`): `image` is a list of n studies, each a list of U{lo..hi} views fp32 [Cin,H,W] U[0,1) whose sizes are
+drawn from `view_sizes`; everything else stays one entry per study (the reference's StudyReportDataset pairs one exam with one report).
 """
 import torch
 
@@ -40,7 +43,10 @@ def image_hw(image_size):
     return int(image_size), int(image_size)
 
 
-def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab_size=28996, seed=42, with_impression=False):
+def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab_size=28996, seed=42, with_impression=False,
+                    views_per_study=None, view_sizes=None):
+    if views_per_study is not None:
+        return _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes)
     g = torch.Generator().manual_seed(seed)
     batch = {}
     if image_size is None:
@@ -59,6 +65,27 @@ def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab
     batch["prompt_labels"] = [{"BenignMalignantDatasetLabels": int(batch["image_label"][i, 0]), "MassShapeLabels": int(shapes[i]),
                                "BIRADS": "unknown" if int(birads[i]) < 0 else str(int(birads[i]))} for i in range(n)]
     return batch
+
+
+def _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes):
+    """n exams of pixels.  Tokens, labels and ids are those of `synthetic_batch(n, image_size=None, ...)` with the same seed (one report per
+    exam); the view counts, sizes and pixels come from a second generator, so the draws of the plain batch are left as they are."""
+    lo, hi = (int(v) for v in views_per_study)
+    if not 1 <= lo <= hi:
+        raise ValueError(f"views_per_study must be (lo, hi) with 1 <= lo <= hi, got {views_per_study!r}")
+    sizes = [image_hw(hw) for hw in view_sizes] if view_sizes else ([image_hw(image_size)] if image_size is not None else [])
+    if not sizes:
+        raise ValueError("a batch of studies needs view_sizes (a list of (H, W) pairs) or an image_size")
+    batch = synthetic_batch(n, S=S, image_size=None, in_chans=in_chans, feature_dim=8, vocab_size=vocab_size, seed=seed,
+                            with_impression=with_impression)
+    del batch["image_features"]
+    g = torch.Generator().manual_seed(seed + 0x5EED)
+    counts = torch.randint(lo, hi + 1, (n,), generator=g).tolist()
+    studies = []
+    for k in counts:
+        which = torch.randint(0, len(sizes), (k,), generator=g).tolist()
+        studies.append([torch.rand(in_chans, *sizes[j], generator=g) for j in which])
+    return {"image": studies, **batch}
 
 
 # label enums of the reference (mmgclip/prompts/enums.py:17-19,29-34) that the validation prompts are built from

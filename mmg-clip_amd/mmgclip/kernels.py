@@ -162,6 +162,28 @@ def avgpool_bwd(dy, n, HW, C, out=None):
     return dx
 
 
+def view_pool_fwd(feat, offsets, S, mode, out=None, argmax=None):
+    """feat fp32 [V,C], offsets int32 [S+1] on the device -> (out fp32 [S,C], argmax int32 [S,C] or None); mode 0 = mean, 1 = max."""
+    V, C = feat.shape
+    assert feat.dtype == torch.float32 and feat.is_contiguous() and offsets.dtype == torch.int32 and offsets.numel() == S + 1
+    _hip.require_gpu(feat, offsets)
+    y = out if out is not None else torch.empty(S, C, device=feat.device, dtype=torch.float32)
+    if mode == 1 and argmax is None:
+        argmax = torch.empty(S, C, device=feat.device, dtype=torch.int32)
+    call("mmg_view_pool_fwd", ptr(feat), ptr(offsets), ptr(y), ptr(argmax) if mode == 1 else None, S, C, mode, stream())
+    return y, (argmax if mode == 1 else None)
+
+
+def view_pool_bwd(dout, offsets, argmax, V, mode, out=None):
+    """dout fp32 [S,C] -> dfeat fp32 [V,C] (argmax: what the max forward returned; None for the mean)."""
+    S, C = dout.shape
+    assert dout.dtype == torch.float32 and dout.is_contiguous() and offsets.dtype == torch.int32 and offsets.numel() == S + 1
+    _hip.require_gpu(dout, offsets)
+    dx = out if out is not None else torch.empty(V, C, device=dout.device, dtype=torch.float32)
+    call("mmg_view_pool_bwd", ptr(dout), ptr(offsets), ptr(argmax), ptr(dx), S, V, C, mode, stream())
+    return dx
+
+
 def patchify(img, P, Kp, scale16):
     n, Cin, H, W = img.shape
     out = torch.empty(n * (H // P) * (W // P), Kp, device=img.device, dtype=BF16)

@@ -15,6 +15,7 @@ import torch
 from ..utils.global_utils import create_directory_if_not_exists
 from ..utils.logger import logger
 from .encoder import ConvNextTiny
+from .view_pool import normalize_method, pool_views
 
 
 def load_image(path):
@@ -130,16 +131,13 @@ class StudyFeatureExtractor:
                 try:
                     names = os.listdir(study_path)[:n_views]
                     feats = self._encode_views([os.path.join(study_path, n) for n in names])
-                    if method == "maxpool":
-                        joint = torch.stack(feats, dim=0).max(dim=0)[0]
-                    elif method == "concat":
+                    kind = normalize_method(method)                  # raises the reference's ValueError for an unknown method
+                    if kind == "concat":
                         joint = torch.cat(feats, dim=0)
-                    elif method == "stack":
+                    elif kind == "stack":
                         joint = torch.stack(feats, dim=0)
-                    elif method == "avgpool":
-                        joint = torch.stack(feats, dim=0).mean(dim=0)
-                    else:
-                        raise ValueError("Not implemented feature vector concatenation method")
+                    else:                                            # maxpool / avgpool: the arithmetic the model applies in training
+                        joint = pool_views(torch.stack(feats, dim=0), [len(feats)], kind)[0]
                     rel = study_path.split('2D_100micron/')[-1] if '2D_100micron/' in study_path else os.path.basename(study_path.rstrip('/'))
                     out_dir = os.path.join(self.export_dir, rel)
                     create_directory_if_not_exists(out_dir)

@@ -21,6 +21,7 @@ from ..utils.logger import logger
 from .bert import EosPool
 from .network_controller import getNetworkClass
 from .projection_controller import get_projection_head
+from .view_pool import normalize_method, offsets_to_device, pool_views, study_offsets
 
 PIXEL_ENCODERS = ("ConvNextTinyEncoder", "ConvNextBaseEncoder", "ViTB16Encoder")
 
@@ -50,8 +51,10 @@ class MMGCLIP(nn.Module):
                 pretrained=True, image_features_dimension=self.config.networks.image_encoder.image_features_dimension).to(self.device)
         elif enc_name in PIXEL_ENCODERS:
             ie = self.config.networks.image_encoder
+            # (stack / concat of a study's k views: image_features_dimension is k x the tower's width, checked at the first batch of studies)
+            joined = self._view_method() in ("stack", "concat")
             self.image_encoder = getNetworkClass(enc_name)(
-                pretrained=_get(ie, "pretrained_path"), image_features_dimension=ie.image_features_dimension,
+                pretrained=_get(ie, "pretrained_path"), image_features_dimension=None if joined else ie.image_features_dimension,
                 in_chans=_get(ie, "in_chans", 1), scale16=_get(ie, "scale16", True), micro_batch=_get(ie, "micro_batch", 64),
                 freeze=_get(ie, "freeze", False),
                 checkpoint=_get(ie, "checkpoint", False),
@@ -100,12 +103,60 @@ class MMGCLIP(nn.Module):
         logger.info(f"Total Trainable Params: {total}")
         return total
 
+    def _view_method(self):
+        """dataset.config.concatenate_features_method (avgpool when the dataset has no such key), in view_pool's spelling."""
+        return normalize_method(_get(self.config, "dataset.config.concatenate_features_method", "avgpool"))
+
+    def _encode_studies(self, pix):
+        """A batch of exams: a list of studies, each a non-empty list / tuple of [Cin, H, W] views (sizes may differ inside and across
+        studies), or one [S, k, Cin, H, W] tensor.  The views go through the image tower once, flattened in study order, and
+        `pool_views` joins each study's rows: [V, F] -> [S, F] (stack / concat: [S, k F]).  What the reference does offline under a
+        frozen encoder (StudyFeatureExtractor, mmgclip/networks/image_features.py:187-263), with gradients."""
+        name = self.config.networks.image_encoder.name
+        if torch.is_tensor(pix):
+            counts = [pix.shape[1]] * pix.shape[0]
+            views = pix.reshape(pix.shape[0] * pix.shape[1], *pix.shape[2:])
+        else:
+            if any(not isinstance(s, (list, tuple)) or not s or any(not torch.is_tensor(v) or v.dim() != 3 for v in s) for s in pix):
+                raise ValueError("a batch of studies must be a list of non-empty lists of [Cin, H, W] tensors")
+            counts = [len(s) for s in pix]
+            views = [v for s in pix for v in s]
+            if len({tuple(v.shape) for v in views}) == 1:
+                views = torch.stack(list(views))                    # every view of one size: the towers' 4-D path
+            elif name == "ViTB16Encoder":
+                raise ValueError(f"ViTB16Encoder needs every view at {self.image_encoder.image_size}x{self.image_encoder.image_size} "
+                                 f"(learned positions fix the size), got views of the sizes {sorted({tuple(v.shape[-2:]) for v in views})}")
+        n_max = _get(self.config, "dataset.config.n_images_per_study")
+        if n_max is not None and max(counts) > int(n_max):
+            raise ValueError(f"a study with {max(counts)} views, but dataset.config.n_images_per_study is {n_max}: "
+                             "the dataset cuts a study to its first n views, the model does not")
+        method = self._view_method()
+        offsets = None
+        if method in ("stack", "concat"):
+            if len(set(counts)) == 1:               # (ragged counts: pool_views says so)
+                want, have = counts[0] * self.image_encoder.model_output_dimension, self.config.networks.image_encoder.image_features_dimension
+                if want != have:
+                    raise ValueError(f"concatenate_features_method={method} joins {counts[0]} views of "
+                                     f"{self.image_encoder.model_output_dimension} features each: set "
+                                     f"networks.image_encoder.image_features_dimension={want} (it is {have})")
+        else:                                       # copied before the tower's kernels are enqueued: the pooling launch never waits for it
+            offsets = offsets_to_device(study_offsets(counts), self.device)
+        if torch.is_tensor(views):
+            feat = self.image_encoder(views.to(self.device))
+        else:
+            feat = self.image_encoder([v.to(self.device) for v in views])
+        return pool_views(feat, counts, method, offsets=offsets)
+
     def encode_images(self, batch):
         """[n,1,F,1,1] pre-extracted features -> [n,F] (mmgclip_model.py:76-93); pixel encoders take `batch['image']`
-        (or a 4-D `image_features`) and run the ConvNeXt tower; `batch['image']` may be a list of [Cin,H_i,W_i] tensors of different sizes."""
+        (or a 4-D `image_features`) and run the ConvNeXt tower; `batch['image']` may be a list of [Cin,H_i,W_i] tensors of different sizes,
+        or a batch of exams (a list of lists of views, or a 5-D [S,k,Cin,H,W] tensor): one feature row per study (`_encode_studies`)."""
         name = self.config.networks.image_encoder.name
         if name in PIXEL_ENCODERS:
             pix = batch["image"] if "image" in batch else batch["image_features"]
+            if (torch.is_tensor(pix) and pix.dim() == 5 and "image" in batch) or \
+                    (isinstance(pix, (list, tuple)) and any(isinstance(s, (list, tuple)) for s in pix)):
+                return self._encode_studies(pix)
             if isinstance(pix, (list, tuple)):      # images of different sizes (ConvNeXt towers): [Cin, H_i, W_i] each
                 return self.image_encoder([p.to(self.device) for p in pix])
             return self.image_encoder(pix.to(self.device))

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 from mmgclip.config import compose                                              # noqa: E402
-from mmgclip.dataset.synthetic import SyntheticLoader                           # noqa: E402
+from mmgclip.dataset.synthetic import SyntheticLoader, image_hw                 # noqa: E402
 from mmgclip.experiments.experiments_controller import create_experiment       # noqa: E402
 from mmgclip.networks.mmgclip_model import PIXEL_ENCODERS, _get                # noqa: E402
 from mmgclip.utils.global_utils import seeding                                 # noqa: E402
@@ -33,6 +33,9 @@ def build_loaders(cfg, rank=0):
     if pixels:
         size = _get(cfg, "networks.image_encoder.image_size", 224)           # an int, or [H, W] for rectangular images
         kw.update(image_size=tuple(size) if isinstance(size, (list, tuple)) else size, in_chans=_get(cfg, "networks.image_encoder.in_chans", 1))
+        if _get(cfg, "dataset.config.views_from_pixels", False):             # exams: every sample a list of views, pooled inside the model
+            kw.update(views_per_study=tuple(_get(cfg, "dataset.config.synthetic_views_per_study", (1, 4))),
+                      view_sizes=[tuple(hw) for hw in _get(cfg, "dataset.config.synthetic_view_sizes", None) or [image_hw(kw["image_size"])]])
     else:
         kw.update(feature_dim=cfg.networks.image_encoder.image_features_dimension)
     bt, bv = cfg.dataloader.train.batch_size, cfg.dataloader.valid.batch_size
