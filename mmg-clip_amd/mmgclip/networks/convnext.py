@@ -16,7 +16,8 @@ row-major GEMM and LayerNorm reads contiguous rows; the 2x2/4x4 stride=kernel co
 rows (the LayerNorm kernel writes the patchified layout directly).  Blocks with C <= 384 run LayerNorm + Linear + GELU +
 Linear + layer scale + residual as one fused launch (csrc/cnblock_mlp.hip); for C <= 192 the backward recomputes the hidden
 row on chip.  Saved for backward per block and pixel: block input (C), depthwise output (C) and - only where the backward
-does not recompute it - the pre-GELU hidden (4C) in bf16 + LN statistics; LN output and GELU output are rebuilt.
+does not recompute it - the pre-GELU hidden (4C) in bf16 + LN statistics; LN output and GELU output are rebuilt, or kept while they fit.
+Which form a block takes, and what it keeps, is decided in convnext_plan.py (table: DESIGN.md section 3).
 
 Image sizes: any H, W >= 32, forward and backward.  Every strided layer floors (stem H // 4, downsample // 2) and drops the odd last row /
 column as torch's convolutions do; the forward records each stage's map size and the backward reads it back (dropped pixels get a zero
@@ -31,7 +32,9 @@ import torch.nn as nn
 from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
+from .._hip import call, ptr, stream
 from ..params import ParamArena, backward_finished, last_backward, note_forward, stream_anchor
+from .convnext_plan import BlockSaved, Knobs, decide_saves, fused_forward, plan_block, saving_form
 
 CONFIGS = {
     "tiny": dict(depths=(3, 3, 9, 3), dims=(96, 192, 384, 768)),
@@ -39,6 +42,11 @@ CONFIGS = {
     "base": dict(depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024)),
 }
 LN_EPS = 1e-6
+
+
+def _fused_save_maxc():
+    """MMG_MLP_FUSED_SAVE_MAXC (A/B knob, round 4; BlockPlan.fused_save_maxc).  Read per forward: tools/ flip it within a process."""
+    return int(os.environ.get("MMG_MLP_FUSED_SAVE_MAXC", "384"))
 
 
 class LayerNorm2d(nn.LayerNorm):
@@ -97,14 +105,12 @@ class ConvNextTower(nn.Module):
         self.fused_mlp = (os.environ.get("MMG_FUSED_MLP", "1") != "0") if fused_mlp is None else bool(fused_mlp)
         self.fused_bwd_saved_h = os.environ.get("MMG_FUSED_MLP_BWD_SAVED_H", "0") == "1"
         self.bwdw = os.environ.get("MMG_BWDW", "1") != "0"        # on-chip weight-gradient backward where supported (csrc/cnblock_bwdw.hip)
-        # blocks whose backward is the GEMM pair keep their LayerNorm output ([M,C] bf16) instead of recomputing it - decided per forward:
-        # only while those copies stay below 4 % of the device memory (C2: 8.4 GB on; ConvNeXt-B at 256 images without checkpointing:
-        # 31 GB on top of 267 GiB of activations, off).  MMG_SAVE_LN=0 / 1 force it.
+        # blocks whose backward is the GEMM pair keep their LayerNorm output ([M,C] bf16) instead of recomputing it, and GELU(hidden)
+        # ([M,4C] bf16), so that the backward's data-gradient GEMM applies GELU' only (its epilogue is VALU-bound and half of it rebuilt that
+        # activation) - decided per forward, while those copies fit the device (convnext_plan.decide_saves).  MMG_SAVE_LN / MMG_SAVE_GELU
+        # = 0 / 1 force them.  save_ln, save_gelu (and fp8_bwd_now below) show what the latest recorded forward decided.
         self.save_ln_mode = os.environ.get("MMG_SAVE_LN", "auto")
         self.save_ln = self.save_ln_mode == "1"
-        # the same blocks also keep GELU(hidden) ([M,4C] bf16) from the forward, so that the backward's data-gradient GEMM applies GELU' only
-        # (its epilogue is VALU-bound and half of it rebuilt that activation) - decided per forward like save_ln, while those copies stay
-        # below 15 % of the device memory (C2: 33.8 GB on; ConvNeXt-B without checkpointing: 131 GB, off).  MMG_SAVE_GELU=0 / 1 force it.
         self.save_gelu_mode = os.environ.get("MMG_SAVE_GELU", "auto")
         self.save_gelu = self.save_gelu_mode == "1"
         # with GELU(h) kept, keep GELU'(h) instead of h as the second 4C-wide tensor (round 4; MMG_SAVE_DGELU=0: h, and the polynomial in the backward)
@@ -117,8 +123,10 @@ class ConvNextTower(nn.Module):
         # round 4: the same blocks' BACKWARD in 8 bits too (MMG_FP8_BWD=0: the bf16 backward of rounds 1 - 3): the incoming gradient is cast to e5m2
         # with a per-tensor power-of-two scale, both data-gradient GEMMs run on e5m2 x e4m3 operands (dh handed on in e5m2, written once), both
         # weight-gradient GEMMs on the 8-bit operands the forward / data path already hold (csrc/gemm_tn_fp8.hip)
-        self.fp8_bwd = os.environ.get("MMG_FP8_BWD", "1") != "0"
-        self.fp8_bwd_now = False             # decided per forward (_decide_save_ln): the 8-bit operands are kept only while they fit
+        # MMG_FP8_BWD: 0 off, 1 always, otherwise (the default) decided per forward - the 8-bit operands are kept only while they fit
+        self.fp8_bwd_mode = os.environ.get("MMG_FP8_BWD", "auto")
+        self.fp8_bwd = self.fp8_bwd_mode != "0"
+        self.fp8_bwd_now = False
         self.fp8_delayed = os.environ.get("MMG_FP8_DELAYED", "1") != "0"      # gradient scale from the previous quantisation of the same tensor role
         self._e5m2_state = {}
         # (round 4, with the 8-bit backward: 256 - same-box A/B of `bench.py --variant base --fp8 --checkpoint`: 925 ms/step from C = 256, 939 from 512,
@@ -131,6 +139,7 @@ class ConvNextTower(nn.Module):
         self._arena = None
         self._wc = None
         self._wc_version = None
+        self.plan = None                    # one BlockPlan per stage; made with the working copies (knobs may be set after construction)
         self._anchor = None
         self.post_backward_hook = None      # called with the arena once this tower's gradients are complete
 
@@ -141,96 +150,118 @@ class ConvNextTower(nn.Module):
         self._arena = ParamArena(list(self.model.named_parameters()), device)
         self._wc_version = None
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
+        self._pname = {id(m): "features." + n for n, m in self.model.features.named_modules()}
 
     @property
     def arena(self):
         return self._arena
 
-    def _fp8_block(self, C):
-        return self.fp8 and C % 128 == 0 and C >= self.fp8_min_channels
+    def _g(self, mod, leaf):
+        """Gradient view (arena) of parameter `leaf` of module `mod`."""
+        return self._arena.g(self._pname[id(mod)] + "." + leaf)
+
+    def knobs(self):
+        return Knobs(self.fp8, self.fp8_min_channels, self.fp8_bwd, self.fused_mlp, self.fused_bwd_saved_h, self.bwdw, _fused_save_maxc())
+
+    def _plan_blocks(self):
+        return tuple(plan_block(C, self.knobs()) for C in self.dims)
 
     def _refresh_working_copies(self):
-        """bf16 / transposed / tap-major copies the kernels read; rebuilt only when a parameter changed."""
+        """bf16 / transposed / tap-major copies the kernels read; rebuilt only when a parameter changed.  Which copies a block gets follows
+        from its BlockPlan (self.plan, made here)."""
         A = self._arena
         v = A.version()
         if self._wc_version == v:
             return
         f = self.model.features
+        plan = self._plan_blocks()
         wc = {}
         stem = f[0][0].weight.data                                   # [C0, Cin, 4, 4] -> [(kh,kw,ci)] padded
         w = torch.zeros(stem.shape[0], self.kp, device=stem.device)
         w[:, :16 * self.in_chans] = stem.permute(0, 2, 3, 1).reshape(stem.shape[0], -1)
         wc["stem.w"] = K.cast_bf16(w)
-        for si in range(4):
+        for si, p in enumerate(plan):
+            C = p.C
             for bi, blk in enumerate(f[1 + 2 * si]):
-                C = self.dims[si]
                 key = f"{si}.{bi}"
+                w1, w2, gamma = blk.block[3].weight.data, blk.block[5].weight.data, blk.layer_scale.data.reshape(C)
                 wc[key + ".w49"] = blk.block[0].weight.data.reshape(C, 49).t().contiguous()
-                wc[key + ".w1"] = K.cast_bf16(blk.block[3].weight.data)                      # [4C, C]
-                wc[key + ".w1t"] = K.transpose_cast_bf16(blk.block[3].weight.data)           # [C, 4C]
-                wc[key + ".w2"] = K.cast_bf16(blk.block[5].weight.data)                      # [C, 4C]
-                wc[key + ".w2gt"] = K.transpose_cast_bf16(blk.block[5].weight.data,          # [4C, C] * gamma
-                                                          blk.layer_scale.data.reshape(C))
-                if self._fp8_block(C):                                                       # e4m3 bytes + (scale, 1/scale)
-                    wc[key + ".w1f8"], wc[key + ".s1"] = K.quantize_e4m3(blk.block[3].weight.data)
-                    wc[key + ".w2f8"], wc[key + ".s2"] = K.quantize_e4m3(blk.block[5].weight.data)
-                    if self.fp8_bwd:         # the data-gradient GEMMs' weights: (gamma W2)^T [4C, C] and W1^T [C, 4C], e4m3 + (scale, 1/scale)
-                        wc[key + ".w2gt8"], wc[key + ".s2gt"] = K.quantize_e4m3(
-                            (blk.block[5].weight.data * blk.layer_scale.data.reshape(C, 1)).t().contiguous())
-                        wc[key + ".w1t8"], wc[key + ".s1t"] = K.quantize_e4m3(blk.block[3].weight.data.t().contiguous())
-                elif self.fused_mlp and K.cnblock_supported(C):                              # packed LDS images
-                    wc[key + ".mlp"] = K.cnblock_pack(blk.block[3].weight.data, blk.block[5].weight.data)
-                    mode = K.cnblock_bwd_mode(C)     # 1: hidden row recomputed; 2: reads the forward's saved pre-activation
-                    if mode == 2 and not self.fused_bwd_saved_h:   # (C=384: slower than the GEMM pair so far)
-                        mode = 0
-                    if mode:
-                        wc[key + (".mlpb" if mode == 1 else ".mlpb2")] = K.cnblock_pack(
-                            blk.block[3].weight.data, blk.block[5].weight.data, blk.layer_scale.data.reshape(C), backward=mode)
-                    # round 3: backward with the weight gradients accumulated on chip (C = 96: nothing 4C-wide reaches HBM)
-                    if mode == 1 and self.bwdw and K.cnblock_bwdw_supported(C, 64):
-                        wc[key + ".bwdw"] = K.cnblock_bwdw_pack(blk.block[3].weight.data, blk.block[5].weight.data, blk.block[2].weight.data,
-                                                                blk.block[2].bias.data, blk.layer_scale.data.reshape(C), blk.block[3].bias.data)
+                wc[key + ".w1"] = K.cast_bf16(w1)                                            # [4C, C]
+                wc[key + ".w1t"] = K.transpose_cast_bf16(w1)                                 # [C, 4C]
+                wc[key + ".w2"] = K.cast_bf16(w2)                                            # [C, 4C]
+                wc[key + ".w2gt"] = K.transpose_cast_bf16(w2, gamma)                         # [4C, C] * gamma
+                if p.kind == "fp8":                                                          # e4m3 bytes + (scale, 1/scale)
+                    wc[key + ".w1f8"], wc[key + ".s1"] = K.quantize_e4m3(w1)
+                    wc[key + ".w2f8"], wc[key + ".s2"] = K.quantize_e4m3(w2)
+                    if p.fp8_bwd_weights:    # the data-gradient GEMMs' weights: (gamma W2)^T [4C, C] and W1^T [C, 4C], e4m3 + (scale, 1/scale)
+                        wc[key + ".w2gt8"], wc[key + ".s2gt"] = K.quantize_e4m3((w2 * gamma.reshape(C, 1)).t().contiguous())
+                        wc[key + ".w1t8"], wc[key + ".s1t"] = K.quantize_e4m3(w1.t().contiguous())
+                elif p.kind == "fused":                                                      # packed LDS images
+                    wc[key + ".mlp"] = K.cnblock_pack(w1, w2)
+                    if p.fused_bwd:
+                        wc[key + ".mlpb"] = K.cnblock_pack(w1, w2, gamma, backward=p.fused_bwd)
+                    if p.bwdw:               # round 3: backward with the weight gradients accumulated on chip (C = 96: nothing 4C-wide reaches HBM)
+                        wc[key + ".bwdw"] = K.cnblock_bwdw_pack(w1, w2, blk.block[2].weight.data, blk.block[2].bias.data, gamma,
+                                                                blk.block[3].bias.data)
             if si < 3:
                 conv = f[2 + 2 * si][1].weight.data                                          # [2C, C, 2, 2]
                 wds = conv.permute(0, 2, 3, 1).reshape(conv.shape[0], -1).contiguous()       # [(kh,kw,ci)]
                 wc[f"ds{si}.w"] = K.cast_bf16(wds)
                 wc[f"ds{si}.wt"] = K.transpose_cast_bf16(wds)
-        self._wc, self._wc_version = wc, v
+        self._wc, self._wc_version, self.plan = wc, v, plan
 
-    def _decide_save_ln(self, n_alive, H, W, device, ckpt=False, more=()):
-        """n_alive = images whose saved tensors are alive at once (the whole batch; one micro-batch under checkpointing).
-        more: further (n_alive, H, W) triples alive at the same time (a batch of several image sizes).
-        ckpt: under checkpointing the saved tensors of ONE micro-batch are all the activation memory there is, so the optional copies may take a
-        larger share of the device (round 4, ConvNeXt-B in micro-batches of 128: 264 against 249 pairs/s with them, peak 238 GiB)."""
-        extra, keep8 = 0, 0
-        for n_alive, H, W in ((n_alive, H, W),) + tuple(more):
-            hh, ww = H // 4, W // 4
-            for si in range(4):
-                C = self.dims[si]
-                if not (K.cnblock_supported(C) and K.cnblock_bwd_mode(C) == 1) and not (K.cnblock_bwd_mode(C) == 2 and self.fused_bwd_saved_h):
-                    extra += self.depths[si] * n_alive * hh * ww * C * 2
-                if self.fp8 and self.fp8_bwd and C % 128 == 0 and C >= self.fp8_min_channels:
-                    keep8 += self.depths[si] * n_alive * hh * ww * C * 5
-                hh, ww = hh // 2, ww // 2
-        total = torch.cuda.get_device_properties(device).total_memory
-        # 8-bit backward: its forward keeps the e4m3 LayerNorm output and activation (5 C bytes per row and block on top of the bf16 side output)
-        # - only while that stays below 15 % of the device memory (C5, checkpointed micro-batches of 64: 23 GB, on; ConvNeXt-B at 256 images
-        # without checkpointing: 93 GB on top of 267 GiB, off - that forward then saves what rounds 1 - 3 saved and its backward runs in bf16)
-        mode8 = os.environ.get("MMG_FP8_BWD", "auto")
-        self.fp8_bwd_now = self.fp8 and self.fp8_bwd and (mode8 == "1" or keep8 <= (0.20 if ckpt else 0.15) * total)
-        if self.save_ln_mode in ("0", "1"):
-            ln = self.save_ln_mode == "1"
+    def _decide_saves(self, n_alive, H, W, device, ckpt=False, more=()):
+        """-> SaveDecision of a forward whose saved tensors of n_alive H x W images (and of `more`: further (n, H, W) triples, a batch of several
+        image sizes) are alive at once; ckpt: they are one checkpointed micro-batch's.  (A tower that has not run yet is planned as it stands.)"""
+        return decide_saves(self.plan or self._plan_blocks(), self.depths, ((n_alive, H, W),) + tuple(more),
+                            torch.cuda.get_device_properties(device).total_memory, ckpt, self.save_ln_mode, self.save_gelu_mode,
+                            self.fp8_bwd_mode if self.fp8 else "0")
+
+    # ---- one block's MLP, forward: -> (block output, BlockSaved or None) ---------------------------------------
+    def _saving(self, p, dec, M):
+        return saving_form(p, dec, M, self.save_dgelu) if dec is not None else (None, None, False, False)
+
+    def _fwd_fused(self, x, d, blk, key, p, dec):
+        """LN + Linear + GELU + Linear + layer scale + residual in one launch.  A GEMM-pair backward (C = 384 by default) gets its optional
+        tensors from the forward's registers: the LayerNorm output as one [M,C] store instead of a LayerNorm pass over d in the backward,
+        GELU(hidden) as the second GEMM consumed it."""
+        bwd, aux_kind, keep_ln, keep_g = self._saving(p, dec, d.shape[0])
+        keep = aux_kind is not None
+        outs = K.cnblock_mlp_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, self._wc[key + ".mlp"],
+                                 blk.block[3].bias.data, blk.block[5].bias.data, blk.layer_scale.data.reshape(p.C), x,
+                                 want_hpre=keep, want_stats=keep, want_xln=keep_ln, want_gact=keep_g, hpre_kind=1 if aux_kind == "dgelu" else 0)
+        xn, hpre, mean, rstd = outs[:4]
+        if dec is None:
+            return xn, None
+        return xn, BlockSaved(x, d, mean, rstd, hpre, aux_kind, outs[4] if keep_ln else None, outs[-1] if keep_g else None, bwd)
+
+    def _fwd_gemm(self, x, d, blk, key, p, dec):
+        """LayerNorm, then the two pointwise GEMMs with GELU / layer scale + residual in their epilogues; bf16 or (fp8 blocks) e4m3 operands,
+        fp32 accumulate.  The 4C-wide side output (the pre-activation, or GELU' of it) is bf16 in both."""
+        C, wc, save = p.C, self._wc, dec is not None
+        bwd, aux_kind, keep_ln, keep_g = self._saving(p, dec, d.shape[0])
+        hpre = torch.empty(x.shape[0], 4 * C, device=x.device, dtype=torch.bfloat16) if save else None
+        epi = L.EPI_GELU_DAUX if aux_kind == "dgelu" else L.EPI_GELU
+        if p.kind == "fp8":
+            ln, mean, rstd = K.layernorm_fwd_fp8(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
+            g = L.gemm_nt_fp8(ln, wc[key + ".w1f8"], bias=blk.block[3].bias.data, aux_out=hpre, epi=epi, out_kind=L.OUT_E4M3,
+                              alpha_dev=wc[key + ".s1"][1:])
+            xn = L.gemm_nt_fp8(g, wc[key + ".w2f8"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C),
+                               residual=x, alpha_dev=wc[key + ".s2"][1:])
         else:
-            ln = extra <= (0.10 if ckpt else 0.04) * total
-        if self.save_gelu_mode in ("0", "1"):
-            self.save_gelu = self.save_gelu_mode == "1"
-        else:
-            self.save_gelu = 4 * extra <= (0.30 if ckpt else 0.15) * total            # ([M,4C] against [M,C])
-        return ln
+            ln, mean, rstd = K.layernorm_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
+            g = L.gemm_nt(ln, wc[key + ".w1"], bias=blk.block[3].bias.data, aux_out=hpre, epi=epi)
+            xn = L.gemm_nt(g, wc[key + ".w2"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C), residual=x)
+        if not save:
+            return xn, None
+        return xn, BlockSaved(x, d, mean, rstd, hpre, aux_kind, ln if keep_ln else None, g if keep_g else None, bwd)
 
     # ---- forward / backward over one micro-batch -----------------------------------------------------------
-    def _forward_mb(self, img, save):
+    def _forward_mb(self, img, plan, dec):
+        """plan: the tower's BlockPlans as the recorded forward this pass belongs to read them; dec: that forward's SaveDecision, or None
+        when this pass saves nothing (no gradient wanted, or a checkpointed micro-batch whose forward runs again in the backward)."""
         f, wc = self.model.features, self._wc
+        save = dec is not None
         n, _, H, W = img.shape
         h, w_ = H // 4, W // 4
         saved = {"maps": [(h, w_)]}                 # map size per stage: floored at every stride, so the backward reads them back
@@ -239,59 +270,14 @@ class ConvNextTower(nn.Module):
         x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
         if save:
             saved["stem"] = (p0, s0, mean, rstd)
-        for si in range(4):
-            C = self.dims[si]
+        for si, p in enumerate(plan):
+            mlp = self._fwd_fused if fused_forward(p, save) else self._fwd_gemm
             for bi, blk in enumerate(f[1 + 2 * si]):
                 key = f"{si}.{bi}"
-                d = K.dwconv7(x, wc[key + ".w49"], blk.block[0].bias.data, n, h, w_, C)
-                # LN + Linear + GELU + Linear + layer scale + residual in one launch (C = 512, ConvNeXt-B stage 3: only when nothing
-                # is saved for a backward - with the 4C-wide pre-activation store it is no faster than the GEMM pair)
-                # MMG_MLP_FUSED_SAVE_MAXC (A/B knob, round 4): widest block whose SAVING forward stays on the fused kernel - at C = 384 that kernel
-                # stores three 4C- / C-wide streams beside its output and the GEMM pair (256 x 256 and 256 x 192 tiles) is within reach of it
-                if key + ".mlp" in wc and (C <= int(os.environ.get("MMG_MLP_FUSED_SAVE_MAXC", "384")) or not save):
-                    keep = save and key + ".mlpb" not in wc      # the fused backward recomputes the hidden row
-                    # a GEMM-pair backward (C = 384 by default) also gets the LayerNorm output from the forward's registers: one
-                    # [M,C] store instead of a LayerNorm pass over d in the backward
-                    keep_ln = keep and self.save_ln and key + ".mlpb2" not in wc
-                    # ... and (save_gelu) GELU(hidden) as the second GEMM consumed it: that backward's data-gradient GEMM then applies GELU' only
-                    keep_g = keep and self.save_gelu and key + ".mlpb2" not in wc
-                    # round 4: with GELU(hidden) kept, the second saved 4C-wide tensor is GELU'(hidden) instead of the hidden itself (same bytes): the
-                    # backward's data-gradient GEMM then multiplies by it (NT epilogue 7) instead of evaluating the polynomial per element
-                    outs = K.cnblock_mlp_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, wc[key + ".mlp"],
-                                             blk.block[3].bias.data, blk.block[5].bias.data, blk.layer_scale.data.reshape(C), x,
-                                             want_hpre=keep, want_stats=keep, want_xln=keep_ln, want_gact=keep_g,
-                                             hpre_kind=1 if (keep_g and self.save_dgelu) else 0)
-                    xn, hpre, mean, rstd = outs[:4]
-                    ln = outs[4] if keep_ln else None
-                    gact = outs[-1] if keep_g else None
-                    if save:
-                        saved[key] = (x, d, mean, rstd, hpre, ln, gact)
-                    x = xn
-                    continue
-                hpre = torch.empty(x.shape[0], 4 * C, device=x.device, dtype=torch.bfloat16) if save else None
-                if key + ".w1f8" in wc:      # e4m3 operands, fp32 accumulate; the saved pre-activation stays bf16
-                    ln, mean, rstd = K.layernorm_fwd_fp8(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
-                    # (8-bit backward: the side output is GELU'(h) - its data-gradient GEMM multiplies by it - and the e4m3 LayerNorm output /
-                    #  activation are kept: they ARE the weight-gradient GEMMs' operands)
-                    g = L.gemm_nt_fp8(ln, wc[key + ".w1f8"], bias=blk.block[3].bias.data, aux_out=hpre,
-                                      epi=L.EPI_GELU_DAUX if (save and self.fp8_bwd_now and key + ".w2gt8" in wc) else L.EPI_GELU,
-                                      out_kind=L.OUT_E4M3, alpha_dev=wc[key + ".s1"][1:])
-                    xn = L.gemm_nt_fp8(g, wc[key + ".w2f8"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C),
-                                       residual=x, alpha_dev=wc[key + ".s2"][1:])
-                else:
-                    ln, mean, rstd = K.layernorm_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
-                    g = L.gemm_nt(ln, wc[key + ".w1"], bias=blk.block[3].bias.data, aux_out=hpre,
-                                  epi=L.EPI_GELU_DAUX if (save and self.save_gelu and self.save_dgelu) else L.EPI_GELU)   # (hpre = GELU'(h) then)
-                    xn = L.gemm_nt(g, wc[key + ".w2"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C),
-                                   residual=x)
-                if save:                         # (an e4m3 LayerNorm output / activation is not what the bf16 backward reads: those are recomputed)
-                    if self.fp8_bwd_now and key + ".w2gt8" in wc:
-                        saved[key] = (x, d, mean, rstd, hpre, ln, g)         # (uint8 tensors: the 8-bit backward below)
-                    else:
-                        saved[key] = (x, d, mean, rstd, hpre, ln if (self.save_ln and ln.dtype == torch.bfloat16) else None,
-                                      g if (self.save_gelu and g.dtype == torch.bfloat16) else None)
-                del ln, g
-                x = xn
+                d = K.dwconv7(x, wc[key + ".w49"], blk.block[0].bias.data, n, h, w_, p.C)
+                x, rec = mlp(x, d, blk, key, p, dec)
+                if save:
+                    saved[key] = rec
             if si < 3:
                 lnm = f[2 + 2 * si][0]
                 ld, mean, rstd = K.layernorm_fwd(x, lnm.weight.data, lnm.bias.data, LN_EPS, patch_hw=(h, w_), want_stats=save)
@@ -305,6 +291,66 @@ class ConvNextTower(nn.Module):
         saved["shape"] = (n, H, W)
         return feat, saved
 
+    # ---- one block's MLP, backward: (dx, rec, blk, key, tmp) -> dd, the gradient w.r.t. the depthwise output -----------------
+    def _ln_bwd(self, dln, d, mean, rstd, blk):
+        return K.layernorm_bwd(dln, d, mean, rstd, blk.block[2].weight.data, self._g(blk.block[2], "weight"), self._g(blk.block[2], "bias"))
+
+    def _bwd_bwdw(self, dx, rec, blk, key, tmp):
+        """Stage 1: data path AND both weight gradients in two launches that read dx, d and write dd - the g / dh tensors ([M,4C] each) of
+        the fused form below and its two weight-gradient GEMMs do not exist."""
+        packed, b1f = self._wc[key + ".bwdw"]
+        return K.cnblock_bwdw(dx, rec.d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, packed, b1f,
+                              self._g(blk.block[3], "weight"), self._g(blk.block[3], "bias"), tmp[key + ".dw2raw"], tmp[key + ".db2raw"],
+                              self._g(blk.block[2], "weight"), self._g(blk.block[2], "bias"))
+
+    def _bwd_fused(self, dx, rec, blk, key, tmp):
+        """Fused data path (hidden row recomputed on chip, or - rec.aux - read back) + the two weight-gradient GEMMs."""
+        # C <= 128: the LayerNorm backward rides in the epilogue (`dd` comes back instead of d LN-out); wider blocks have no registers
+        # left for it
+        fuse_ln = rec.d.shape[1] <= 128
+        dh, g, ln, dln, mean, rstd = K.cnblock_mlp_bwd(
+            dx, rec.d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, self._wc[key + ".mlpb"], blk.block[3].bias.data, rec.aux,
+            ln_grads=(self._g(blk.block[2], "weight"), self._g(blk.block[2], "bias")) if fuse_ln else None)
+        L.gemm_tn_acc(dx, g, tmp[key + ".dw2raw"], colsum=tmp[key + ".db2raw"])
+        del g
+        L.gemm_tn_acc(dh, ln, self._g(blk.block[3], "weight"), colsum=self._g(blk.block[3], "bias"))
+        del ln, dh
+        return dln if fuse_ln else self._ln_bwd(dln, rec.d, mean, rstd, blk)
+
+    def _bwd_fp8(self, dx, rec, blk, key, tmp):
+        """8-bit backward (config C5): rec.aux holds GELU'(h) (bf16), rec.ln / rec.g the e4m3 operands of the forward GEMMs."""
+        wc = self._wc
+        # (delayed scaling from the second use on: the scale of this block's gradient comes from its previous quantisation - one pass)
+        # (+ the bias gradient of the second Linear = column sums of the bf16 gradient itself, in the same pass over it)
+        dy8, sdy = K.quantize_e5m2(dx, self._e5m2_state.setdefault(key, {}) if self.fp8_delayed else None, colsum=tmp[key + ".db2raw"])
+        dh8 = L.gemm_nt_fp8_bwd(dy8, wc[key + ".w2gt8"], aux_in=rec.aux, epi=L.EPI_MUL_AUX, out_kind=L.OUT_E5M2,
+                                alpha_dev=wc[key + ".s2gt"][1:])               # e5m2 at dy's scale: (acc / s_w) * GELU'
+        L.gemm_tn_fp8_acc(dy8, rec.g, tmp[key + ".dw2raw"], alpha_dev=sdy[1:])
+        L.gemm_tn_fp8_acc(dh8, rec.ln, self._g(blk.block[3], "weight"), alpha_dev=sdy[1:], colsum=self._g(blk.block[3], "bias"))
+        dln = L.gemm_nt_fp8_bwd(dh8, wc[key + ".w1t8"], alpha_dev=wc[key + ".s1t"][1:], alpha_dev2=sdy[1:])
+        del dh8, dy8
+        return self._ln_bwd(dln, rec.d, rec.mean, rec.rstd, blk)
+
+    def _bwd_gemm(self, dx, rec, blk, key, tmp):
+        """GEMM pair, bf16, on the saved 4C-wide tensor(s)."""
+        wc = self._wc
+        if rec.g is not None:                  # the forward kept GELU(h): GELU' only (half the epilogue's arithmetic and stores)
+            g = rec.g
+            # ... and (aux_kind "dgelu") GELU'(h) in place of h: one multiply per element
+            dh = L.gemm_nt(dx, wc[key + ".w2gt"], epi=L.EPI_MUL_AUX if rec.aux_kind == "dgelu" else L.EPI_DGELU_ONLY, aux_in=rec.aux)
+        else:
+            g = torch.empty_like(rec.aux)      # GELU(h), rebuilt by the same epilogue that applies GELU'
+            dh = L.gemm_nt(dx, wc[key + ".w2gt"], epi=L.EPI_DGELU, aux_in=rec.aux, aux_out=g)
+        L.gemm_tn_acc(dx, g, tmp[key + ".dw2raw"], colsum=tmp[key + ".db2raw"])
+        del g
+        ln = rec.ln if rec.ln is not None else \
+            K.layernorm_fwd(rec.d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=False)[0]
+        L.gemm_tn_acc(dh, ln, self._g(blk.block[3], "weight"), colsum=self._g(blk.block[3], "bias"))
+        del ln
+        dln = L.gemm_nt(dh, wc[key + ".w1t"])
+        del dh
+        return self._ln_bwd(dln, rec.d, rec.mean, rec.rstd, blk)
+
     def _backward_mb(self, dfeat, saved, tmp, final=False, announce=False):
         """final: last micro-batch of this backward - the GEMM-shaped temporaries of a stage are folded into the torch-layout
         gradients as soon as the stage has passed; announce: it is also the tower's last backward of the step, so the stage's
@@ -314,77 +360,24 @@ class ConvNextTower(nn.Module):
         n, H, W = saved["shape"]
         maps = saved["maps"]
         h, w_ = maps[3]
-        gname = lambda mod, leaf: A.g(self._pname[id(mod)] + "." + leaf)      # noqa: E731
         dx = K.avgpool_bwd(dfeat, n, h * w_, self.dims[-1])
         for si in range(3, -1, -1):
             C = self.dims[si]
             if si < 3:
                 x, mean, rstd, ld = saved[f"ds{si}"]
                 conv, lnm = f[2 + 2 * si][1], f[2 + 2 * si][0]
-                L.gemm_tn_acc(dx, ld, tmp[f"ds{si}.dw"], colsum=gname(conv, "bias"))
+                L.gemm_tn_acc(dx, ld, tmp[f"ds{si}.dw"], colsum=self._g(conv, "bias"))
                 dld = L.gemm_nt(dx, wc[f"ds{si}.wt"])
                 h, w_ = maps[si]                   # (odd sizes: the dropped last row / column gets a zero gradient here)
-                dx = K.layernorm_bwd(dld, x, mean, rstd, lnm.weight.data, gname(lnm, "weight"), gname(lnm, "bias"),
+                dx = K.layernorm_bwd(dld, x, mean, rstd, lnm.weight.data, self._g(lnm, "weight"), self._g(lnm, "bias"),
                                      patch_hw=(h, w_))
                 del dld
             for bi in range(self.depths[si] - 1, -1, -1):
                 blk = f[1 + 2 * si][bi]
                 key = f"{si}.{bi}"
-                x, d, mean, rstd, hpre, ln_saved, g_saved = saved[key]
-                if hpre is None and key + ".bwdw" in wc and K.cnblock_bwdw_supported(C, d.shape[0]):
-                    # stage 1: data path AND both weight gradients in two launches that read dx, d and write dd - the g / dh tensors
-                    # ([M,4C] each) of the path below and its two weight-gradient GEMMs do not exist
-                    packed, b1f = wc[key + ".bwdw"]
-                    dd = K.cnblock_bwdw(dx, d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, packed, b1f,
-                                        gname(blk.block[3], "weight"), gname(blk.block[3], "bias"), tmp[key + ".dw2raw"], tmp[key + ".db2raw"],
-                                        gname(blk.block[2], "weight"), gname(blk.block[2], "bias"))
-                    dln = None
-                elif hpre is None or key + ".mlpb2" in wc:   # fused data path (hidden row recomputed on chip / read back)
-                    # C <= 128: the LayerNorm backward rides in the epilogue (`dd` comes back instead of d LN-out); wider
-                    # blocks have no registers left for it
-                    fuse_ln = C <= 128
-                    dh, g, ln, dln, mean, rstd = K.cnblock_mlp_bwd(
-                        dx, d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS,
-                        wc[key + (".mlpb" if hpre is None else ".mlpb2")], blk.block[3].bias.data, hpre,
-                        ln_grads=(gname(blk.block[2], "weight"), gname(blk.block[2], "bias")) if fuse_ln else None)
-                    if fuse_ln:
-                        dd, dln = dln, None
-                    L.gemm_tn_acc(dx, g, tmp[key + ".dw2raw"], colsum=tmp[key + ".db2raw"])
-                    del g
-                    L.gemm_tn_acc(dh, ln, gname(blk.block[3], "weight"), colsum=gname(blk.block[3], "bias"))
-                    del ln, dh
-                elif g_saved is not None and g_saved.dtype == torch.uint8:
-                    # 8-bit backward (config C5): hpre holds GELU'(h) (bf16), ln_saved / g_saved the e4m3 operands of the forward GEMMs
-                    # (delayed scaling from the second use on: the scale of this block's gradient comes from its previous quantisation - one pass)
-                    # (+ the bias gradient of the second Linear = column sums of the bf16 gradient itself, in the same pass over it)
-                    dy8, sdy = K.quantize_e5m2(dx, self._e5m2_state.setdefault(key, {}) if self.fp8_delayed else None, colsum=tmp[key + ".db2raw"])
-                    dh8 = L.gemm_nt_fp8_bwd(dy8, wc[key + ".w2gt8"], aux_in=hpre, epi=L.EPI_MUL_AUX, out_kind=L.OUT_E5M2,
-                                            alpha_dev=wc[key + ".s2gt"][1:])               # e5m2 at dy's scale: (acc / s_w) * GELU'
-                    L.gemm_tn_fp8_acc(dy8, g_saved, tmp[key + ".dw2raw"], alpha_dev=sdy[1:])
-                    L.gemm_tn_fp8_acc(dh8, ln_saved, gname(blk.block[3], "weight"), alpha_dev=sdy[1:], colsum=gname(blk.block[3], "bias"))
-                    dln = L.gemm_nt_fp8_bwd(dh8, wc[key + ".w1t8"], alpha_dev=wc[key + ".s1t"][1:], alpha_dev2=sdy[1:])
-                    del dh8, dy8
-                else:
-                    if g_saved is not None:                # the forward kept GELU(h): GELU' only (half the epilogue's arithmetic and stores)
-                        g = g_saved
-                        # ... and (save_dgelu) GELU'(h) in place of h: one multiply per element
-                        dh = L.gemm_nt(dx, wc[key + ".w2gt"], epi=L.EPI_MUL_AUX if self.save_dgelu else L.EPI_DGELU_ONLY, aux_in=hpre)
-                    else:
-                        g = torch.empty_like(hpre)         # GELU(hpre), rebuilt by the same epilogue that applies GELU'
-                        dh = L.gemm_nt(dx, wc[key + ".w2gt"], epi=L.EPI_DGELU, aux_in=hpre, aux_out=g)
-                    L.gemm_tn_acc(dx, g, tmp[key + ".dw2raw"], colsum=tmp[key + ".db2raw"])
-                    del g
-                    ln = ln_saved if ln_saved is not None else \
-                        K.layernorm_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=False)[0]
-                    L.gemm_tn_acc(dh, ln, gname(blk.block[3], "weight"), colsum=gname(blk.block[3], "bias"))
-                    del ln
-                    dln = L.gemm_nt(dh, wc[key + ".w1t"])
-                    del dh
-                if dln is not None:
-                    dd = K.layernorm_bwd(dln, d, mean, rstd, blk.block[2].weight.data, gname(blk.block[2], "weight"),
-                                         gname(blk.block[2], "bias"))
-                del dln
-                K.dwconv7_wgrad(x, dd, tmp[key + ".dw49"], gname(blk.block[0], "bias"), n, h, w_, C)
+                rec = saved[key]
+                dd = getattr(self, "_bwd_" + rec.bwd)(dx, rec, blk, key, tmp)
+                K.dwconv7_wgrad(rec.x, dd, tmp[key + ".dw49"], self._g(blk.block[0], "bias"), n, h, w_, C)
                 dx = K.dwconv7(dd, wc[key + ".w49"], None, n, h, w_, C, add=dx, flip=True)
                 del dd
             if final:
@@ -392,8 +385,8 @@ class ConvNextTower(nn.Module):
                 if announce:
                     A.mark_ready((f"features.{1 + 2 * si}.",) + ((f"features.{2 + 2 * si}.",) if si < 3 else ()))
         p0, s0, mean, rstd = saved["stem"]
-        ds0 = K.layernorm_bwd(dx, s0, mean, rstd, f[0][1].weight.data, gname(f[0][1], "weight"), gname(f[0][1], "bias"))
-        L.gemm_tn_acc(ds0, p0, tmp["stem.dw"], colsum=gname(f[0][0], "bias"))
+        ds0 = K.layernorm_bwd(dx, s0, mean, rstd, f[0][1].weight.data, self._g(f[0][1], "weight"), self._g(f[0][1], "bias"))
+        L.gemm_tn_acc(ds0, p0, tmp["stem.dw"], colsum=self._g(f[0][0], "bias"))
         if final:
             self._finalize_stem(tmp)
 
@@ -411,33 +404,28 @@ class ConvNextTower(nn.Module):
 
     def _finalize_stem(self, tmp):
         """Fold the GEMM-shaped stem temporary into the torch-layout gradient."""
-        f, A = self.model.features, self._arena
-        from .._hip import call, ptr, stream
-        stem = f[0][0]
         # the stem temp is [C0, Kp] with zero-padded tail columns: relayout the first 16*Cin columns
         kk = 16 * self.in_chans
         src = tmp["stem.dw"][:, :kk].contiguous()
-        call("mmg_grad_relayout", ptr(src), ptr(A.g(self._pname[id(stem)] + ".weight")), 0, self.dims[0], self.in_chans, 4, 4, kk,
+        call("mmg_grad_relayout", ptr(src), ptr(self._g(self.model.features[0][0], "weight")), 0, self.dims[0], self.in_chans, 4, 4, kk,
              stream())
 
     def _finalize_stage(self, tmp, si):
         """Fold stage si's GEMM-shaped temporaries (and those of the downsample layer behind it) into the torch-layout gradients
         (layer scale, conv layouts)."""
-        f, A = self.model.features, self._arena
-        from .._hip import call, ptr, stream
-        gname = lambda mod, leaf: A.g(self._pname[id(mod)] + "." + leaf)      # noqa: E731
+        f = self.model.features
         C = self.dims[si]
         for bi, blk in enumerate(f[1 + 2 * si]):
             key = f"{si}.{bi}"
             call("mmg_layerscale_finalize", ptr(blk.block[5].weight.data), ptr(blk.block[5].bias.data),
                  ptr(blk.layer_scale.data), ptr(tmp[key + ".dw2raw"]), ptr(tmp[key + ".db2raw"]),
-                 ptr(gname(blk.block[5], "weight")), ptr(gname(blk.block[5], "bias")),
-                 ptr(A.g(self._pname[id(blk)] + ".layer_scale")), C, 4 * C, stream())
-            call("mmg_grad_relayout", ptr(tmp[key + ".dw49"]), ptr(gname(blk.block[0], "weight")), 1, C, 1, 7, 7, C,
+                 ptr(self._g(blk.block[5], "weight")), ptr(self._g(blk.block[5], "bias")),
+                 ptr(self._g(blk, "layer_scale")), C, 4 * C, stream())
+            call("mmg_grad_relayout", ptr(tmp[key + ".dw49"]), ptr(self._g(blk.block[0], "weight")), 1, C, 1, 7, 7, C,
                  stream())
         if si < 3:
             conv = f[2 + 2 * si][1]
-            call("mmg_grad_relayout", ptr(tmp[f"ds{si}.dw"]), ptr(gname(conv, "weight")), 0, self.dims[si + 1], C, 2, 2,
+            call("mmg_grad_relayout", ptr(tmp[f"ds{si}.dw"]), ptr(self._g(conv, "weight")), 0, self.dims[si + 1], C, 2, 2,
                  4 * C, stream())
 
     # ---- public -----------------------------------------------------------------------------------------------
@@ -467,7 +455,6 @@ class ConvNextTower(nn.Module):
                 raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(images.shape)}")
             device = images.device
         self._materialize(device)
-        self._pname = {id(m): "features." + n for n, m in self.model.features.named_modules()}
         needs_grad = torch.is_grad_enabled() and self._arena.any_trainable()
         note_forward(self, needs_grad)
         anchor = stream_anchor(self, self._anchor.device) if needs_grad else None
@@ -515,8 +502,14 @@ class _ConvNextFn(torch.autograd.Function):
             alive = [(k, hw[0], hw[1]) for hw, k in by_size.items()]
             if ckpt:                        # one micro-batch alive at a time: the largest one decides
                 alive = [max(alive, key=lambda a: a[0] * a[1] * a[2])]
+        # the plan and the decision on what to keep belong to THIS forward: every pass of it, the recomputation inside its backward included,
+        # gets them as arguments (a tower may record several forwards before the first backward)
+        maxc = _fused_save_maxc()
+        blocks = tower.plan = tuple(p._replace(fused_save_maxc=maxc) for p in tower.plan)
+        dec = None
         if save:
-            tower.save_ln = tower._decide_save_ln(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
+            dec = tower._decide_saves(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
+            tower.save_ln, tower.save_gelu, tower.fp8_bwd_now = dec         # (the latest forward's, for whoever reports them: bench.py)
         for k, part in enumerate(parts):
             # gradient checkpointing at micro-batch granularity: keep only the pixels, re-run the micro-batch's forward (with its
             # activations saved) right before its backward - activation memory becomes one micro-batch instead of the whole batch.
@@ -524,11 +517,12 @@ class _ConvNextFn(torch.autograd.Function):
             # micro-batch's activations are alive at any time, and one of the n recomputations is not run (MMG_CKPT_KEEP_LAST=0: all are).
             keep = ckpt and k == len(parts) - 1 and os.environ.get("MMG_CKPT_KEEP_LAST", "1") != "0"
             pix = part()
-            ft, sv = tower._forward_mb(pix, save and (not ckpt or keep))
+            ft, sv = tower._forward_mb(pix, blocks, dec if (not ckpt or keep) else None)
             feats.append(ft)
             saved.append({"recompute": part, "n": pix.shape[0]} if (ckpt and not keep) else sv)     # (the pixels are sliced / stacked again then)
             del pix
         ctx.tower, ctx.saved_mb, ctx.reverse = tower, saved if save else None, ckpt
+        ctx.plan, ctx.decision = blocks, dec
         ctx.inverse = None
         out = torch.cat(feats, 0) if len(feats) > 1 else feats[0]
         if plan is not None and plan[1] != list(range(count)):
@@ -552,7 +546,7 @@ class _ConvNextFn(torch.autograd.Function):
         for pos, k in enumerate(order):
             sv = ctx.saved_mb[k]
             if "recompute" in sv:
-                _, sv = tower._forward_mb(sv["recompute"](), True)
+                _, sv = tower._forward_mb(sv["recompute"](), ctx.plan, ctx.decision)
             i, n = starts[k], sizes[k]
             final = pos == len(order) - 1
             tower._backward_mb(dfeat[i:i + n].contiguous(), sv, tmp, final=final, announce=final and last_backward(tower))

@@ -209,17 +209,16 @@ def test_saved_layernorm_output_is_bounded_by_device_memory(dev):
     of activations), on again for one of its 64-image checkpointed micro-batches."""
     from mmgclip.networks.encoder import ConvNextBaseEncoder, ConvNextTinyEncoder
     tiny, base = ConvNextTinyEncoder(), ConvNextBaseEncoder()
-    assert tiny._decide_save_ln(256, 1024, 1024, dev) is True
-    assert base._decide_save_ln(256, 1024, 1024, dev) is False
-    assert base._decide_save_ln(64, 1024, 1024, dev) is True
+    assert tiny._decide_saves(256, 1024, 1024, dev).save_ln is True
+    assert base._decide_saves(256, 1024, 1024, dev).save_ln is False
+    assert base._decide_saves(64, 1024, 1024, dev).save_ln is True
     # round 4: a checkpointed micro-batch is all the activation memory there is - its optional copies may take a larger share (128 images of
     # ConvNeXt-B: LayerNorm outputs 14.5 GB, GELU 58 GB, the 8-bit operands 46 GB; measured peak 239 / 196 GiB of 288), but not without limit
-    assert base._decide_save_ln(128, 1024, 1024, dev) is False and base.save_gelu is False
-    assert base._decide_save_ln(128, 1024, 1024, dev, ckpt=True) is True and base.save_gelu is True
-    base._decide_save_ln(256, 1024, 1024, dev, ckpt=True)
-    assert base.save_gelu is False
+    dec = base._decide_saves(128, 1024, 1024, dev)
+    assert dec.save_ln is False and dec.save_gelu is False
+    dec = base._decide_saves(128, 1024, 1024, dev, ckpt=True)
+    assert dec.save_ln is True and dec.save_gelu is True
+    assert base._decide_saves(256, 1024, 1024, dev, ckpt=True).save_gelu is False
     f8 = ConvNextBaseEncoder(fp8=True)
-    f8._decide_save_ln(128, 1024, 1024, dev, ckpt=True)
-    assert f8.fp8_bwd_now is True
-    f8._decide_save_ln(256, 1024, 1024, dev)
-    assert f8.fp8_bwd_now is False
+    assert f8._decide_saves(128, 1024, 1024, dev, ckpt=True).fp8_bwd_now is True
+    assert f8._decide_saves(256, 1024, 1024, dev).fp8_bwd_now is False

@@ -153,7 +153,7 @@ def test_convnext_base_fp8_forward_backward_at_a_ragged_size(dev):
     test_convnext_fp8_backward_matches_the_fp8_oracle (every gradient cosine > 0.94, rel < 0.35) for towers with e4m3 beyond the last stage."""
     tower, fr, fc, worst = _tower_vs_oracle(dev, "base", 2, 100, 70, fp8=True)
     assert tower.fp8_bwd and tower.fp8_bwd_now and tower.fp8_min_channels < tower.dims[-1]
-    assert sum(k.endswith(".w2gt8") for k in tower._wc) == sum(d for d, c in zip(tower.depths, tower.dims) if c >= tower.fp8_min_channels)
+    assert sum(d for d, p in zip(tower.depths, tower.plan) if p.fp8_bwd_weights) == sum(d for d, c in zip(tower.depths, tower.dims) if c >= tower.fp8_min_channels)
     gr, gc = max(v[0] for v in worst.values()), min(v[1] for v in worst.values())
     print("native size fp8 base 100x70 feat rel", fr, "cos", fc, "grad rel max", gr, "cos min", gc)
     measured("convnext_native_size", variant="base_fp8", H=100, W=70, n=2, feat_rel=fr, feat_cos=fc, grad_rel_max=gr, grad_cos_min=gc)
