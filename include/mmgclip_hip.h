@@ -181,6 +181,31 @@ int mmg_patchify(const float* img, void* out, int n, int Cin, int H, int W, int 
 int mmg_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, float grad_scale, mmg_stream_t stream);
 
+/* ---- gradient clipping by global norm + non-finite-step guard (csrc/grad_clip.hip) ------------------------------
+ * The reference goes from loss.backward() straight to optimizer.step() (mmgclip/experiments/ClassifierExperiment.py:115-118);
+ * these sit between the two, where a user would call torch.nn.utils.clip_grad_norm_.  Additive entry points: they came
+ * without an ABI version step (mmg_abi_version() stays 5).  No host read-back, no atomics, no memset; bit-reproducible. */
+
+/* Number of per-workgroup partial sums mmg_grad_sumsq writes for n elements: clamp(ceil(n / 8192), 1, 2048); 0 for n <= 0.
+ * A function of n alone (never of the device), so the same gradient gives the same bits everywhere. */
+int mmg_grad_sumsq_partials(long long n);
+/* partials[w] = sum of g[i]^2 over the elements workgroup w reads, squared and accumulated in fp64 (n_partials must equal
+ * mmg_grad_sumsq_partials(n)).  Any n >= 1; g needs 4-byte alignment only (views, 0-d tensors).  Beside
+ * ClassifierExperiment.py:115-118 (additive). */
+int mmg_grad_sumsq(const float* g, long long n, double* partials, int n_partials, mmg_stream_t stream);
+/* The n partials of every gradient buffer of the step (back to back), summed in a fixed order in fp64:
+ *   out[0] = total_norm (fp32),  out[1] = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; exactly 1 for
+ *   max_norm <= 0 or +inf = no clipping),  out[2] = 1 if total_norm is finite as fp32, else 0;
+ * when it is not finite and skipped != NULL: *skipped += 1.  Beside ClassifierExperiment.py:115-118 (additive). */
+int mmg_grad_clip_finalize(const double* partials, int n, float max_norm, float* out, int* skipped, mmg_stream_t stream);
+/* mmg_adamw_step with the gradient scale and the go/no-go taken from the device: clip = the `out` above, g is multiplied by
+ * clip[1]; skipped != NULL: when clip[2] == 0 nothing is written (p, m, v, p_bf16 keep their bits), else the bias corrections
+ * use t = step - *skipped, so a skipped step does not advance Adam's clock; skipped == NULL: always steps, t = step.
+ * Beside ClassifierExperiment.py:115-118 (additive). */
+int mmg_adamw_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, int step, const float* clip, const int* skipped,
+                           mmg_stream_t stream);
+
 /* ConvNeXt layer scale (out = x + gamma * (G W2^T + b2)): converts the unscaled weight-gradient GEMM results
  * dW2raw [C,K], db2raw [C] into dgamma, dW2, db2 (all ACCUMULATED).  torchvision CNBlock.layer_scale. */
 int mmg_layerscale_finalize(const float* W2, const float* b2, const float* gamma, const float* dW2raw,

@@ -7,6 +7,8 @@ offline: SURVEY.md §5).  Implements exactly the subset the reference's configs 
   * `key=value` / `group=option` / `+key=value` command-line overrides;
   * interpolations `${a.b.c}`, `${now:%Y-%m-%d}`, `${hydra:run.dir}`.
 Returns a `Config` (dict with attribute access, like the AttrDict the reference wraps around OmegaConf: train.py:11-14).
+The dotted keys that were set by `key=value` overrides are kept beside it (`overridden_keys(cfg)`, not an item of the dict): an
+option whose shipped default is "on, where it applies" can tell an explicit request from the default.
 """
 import copy
 import datetime
@@ -135,4 +137,11 @@ def compose(config_dir, config_name, overrides=()):
 
     cfg = resolve(cfg)
     cfg.pop("hydra", None)
-    return Config.wrap(cfg)
+    cfg = Config.wrap(cfg)
+    object.__setattr__(cfg, "_overridden", frozenset(k for k, _ in key_over))
+    return cfg
+
+
+def overridden_keys(cfg):
+    """Dotted keys a `compose` caller set with `key=value` overrides (empty for a config built any other way)."""
+    return getattr(cfg, "_overridden", frozenset()) if isinstance(cfg, Config) else frozenset()

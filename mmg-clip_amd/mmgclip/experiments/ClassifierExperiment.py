@@ -6,7 +6,9 @@ optimizer.step(); scheduler stepped ONCE PER EPOCH, so epoch 1 runs at lr 0: SUR
 Scope: the train loop and `validate()` (loss + zero-shot prompt AUROC: 1 malignancy prompt, 4 mass
 shape prompts, 8 BI-RADS prompts; prompt embeddings cached once per call instead of re-encoded per batch) are reproduced;
 `test()` (the offline Evaluator with bootstrap CIs, confusion matrices and plots) is out of scope.
-Additive options: `distributed.global_loss`, `optimizer.config.fused` (FusedAdamW over the parameter arenas).
+Additive options: `distributed.global_loss`, `optimizer.config.fused` (FusedAdamW over the parameter arenas),
+`optimizer.config.max_grad_norm` / `optimizer.config.skip_nonfinite` (clip the gradients by their global norm and do not step on a
+NaN / Inf gradient; the reference goes from backward straight to step, :115-118, and so does a shipped config).
 """
 import os
 import time
@@ -17,6 +19,7 @@ import torch
 os.environ["TOKENIZERS_PARALLELISM"] = "false"
 
 from ..callbacks.early_stopping import EarlyStopper                      # noqa: E402
+from ..config import overridden_keys                                     # noqa: E402
 from ..dataset.synthetic import BENIGN_MALIGNANT, MASS_SHAPES            # noqa: E402
 from ..loss.loss_controller import create_loss                           # noqa: E402
 from ..networks.mmgclip_model import MMGCLIP as model, _get              # noqa: E402
@@ -70,13 +73,24 @@ class ClassifierExperiment:
         logger.info(f"Using {self.criterion.__class__.__name__} loss.")
 
         lr, wd = self.config.optimizer.config.learning_rate, self.config.optimizer.config.weight_decay
+        # gradient clipping / non-finite guard: in force when max_grad_norm is set, or when skip_nonfinite was asked for by an explicit
+        # override without it; the shipped `skip_nonfinite: true` alone says what happens WHEN the guard is in force, so a config
+        # composed as shipped steps exactly as the reference does
+        self.max_grad_norm = _get(config, "optimizer.config.max_grad_norm", None)
+        skip = _get(config, "optimizer.config.skip_nonfinite", True)
+        skip = True if skip is None else bool(skip)
+        if self.max_grad_norm is None:
+            skip = skip and "optimizer.config.skip_nonfinite" in overridden_keys(config)
+        self.skip_nonfinite = skip
+        self.skipped_steps, self._last_grad_norm = 0, None                # (the torch.optim.AdamW path counts on the host)
         if _get(config, "optimizer.config.fused", False):
             # the towers' parameter arenas do not exist yet (they are built at the first forward): FusedAdamW finds them from
             # the parameters at every step.  EVERY parameter is listed, frozen ones included, exactly as the reference hands
             # `model.parameters()` to torch.optim.AdamW (ClassifierExperiment.py:74): the param-group layout of a checkpoint's
             # optimizer_state_dict is then the same in both directions (frozen parameters never get a gradient and are skipped)
             from ..optim import FusedAdamW
-            self.optimizer = FusedAdamW(self.model.parameters(), lr=lr, weight_decay=wd)
+            self.optimizer = FusedAdamW(self.model.parameters(), lr=lr, weight_decay=wd, max_grad_norm=self.max_grad_norm,
+                                        skip_nonfinite=self.skip_nonfinite)
         else:
             self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=lr, weight_decay=wd)
 
@@ -122,6 +136,7 @@ class ClassifierExperiment:
         self.model.train()
         loss_list = []
         parallel = self.comm is not None and self.comm.active
+        guard_here = (self.max_grad_norm is not None or self.skip_nonfinite) and not hasattr(self.optimizer, "skipped_steps")
         for index, batch in enumerate(self.train_dataloader):
             self.optimizer.zero_grad(set_to_none=True)
             if parallel:
@@ -135,12 +150,42 @@ class ClassifierExperiment:
                 self.model.join_streams()                       # (two-stream mode: the text tower's backward ran on a side stream)
             if sync is not None:
                 sync.finish()                                   # every gradient is the all-rank sum before the optimizer reads it
+            # Clipping needs nothing more under data parallelism: the norm is taken here, after GradSync.finish(), on the reduced
+            # gradients, which are the same bits on every rank - so are the norm, the coefficient and the decision to skip.
+            if guard_here and not self._clip_on_host():
+                loss_list.append(loss.item())
+                continue                                        # non-finite gradient norm: no step (FusedAdamW decides on the device)
             self.optimizer.step()
             loss_list.append(loss.item())
         self.scheduler.step()
         epoch_loss = np.mean(loss_list)
         self.writer.add_scalar('loss/train', epoch_loss, self.current_epoch + 1)
+        self._log_grad_guard()
         return epoch_loss
+
+    def _clip_on_host(self):
+        """torch.optim.AdamW path: torch.nn.utils.clip_grad_norm_ over the model's gradients; False = do not step (norm not finite)."""
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else float("inf")
+        self._last_grad_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm)
+        if self.skip_nonfinite and not bool(torch.isfinite(self._last_grad_norm)):
+            self.skipped_steps += 1
+            return False
+        return True
+
+    def _log_grad_guard(self):
+        """End of an epoch, rank 0: the last step's gradient norm and the steps skipped so far (one read-back per epoch)."""
+        if not self._lead or (self.max_grad_norm is None and not self.skip_nonfinite):
+            return
+        if hasattr(self.optimizer, "skipped_steps"):
+            norm, skipped = self.optimizer.grad_norm, self.optimizer.skipped_steps()
+            norm = None if norm is None else float(norm[0])
+        else:
+            norm, skipped = self._last_grad_norm, self.skipped_steps
+            norm = None if norm is None else float(norm)
+        if norm is not None:
+            self.writer.add_scalar('grad_norm/train', norm, self.current_epoch + 1)
+        self.writer.add_scalar('skipped_steps/train', skipped, self.current_epoch + 1)
+        logger.info(f"grad_norm/train {norm} | skipped_steps/train {skipped}")
 
     def _prompt_token_sets(self):
         """{metric: tokens of its k prompts}: the tokenizer when the caller supplied one, else hashed stand-in ids."""

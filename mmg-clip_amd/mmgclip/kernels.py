@@ -196,6 +196,37 @@ def adamw_step(p, g, m, v, p16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0)
          float(eps), float(wd), int(step), float(grad_scale), stream())
 
 
+def grad_sumsq_partials(n):
+    """How many fp64 partial sums `grad_sumsq` writes for n elements (a function of n alone)."""
+    return int(_hip.load().mmg_grad_sumsq_partials(int(n)))
+
+
+def grad_sumsq(g, partials, offset=0, count=None):
+    """partials[offset : offset + count] (fp64) = per-workgroup sums of squares of the contiguous fp32 tensor g (any numel >= 1, 0-d
+    and 4-byte-aligned views included); count defaults to grad_sumsq_partials(g.numel())."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and partials.dtype == torch.float64 and partials.is_contiguous()
+    _hip.require_gpu(g, partials)
+    count = grad_sumsq_partials(g.numel()) if count is None else int(count)
+    assert 0 <= offset and offset + count <= partials.numel()
+    call("mmg_grad_sumsq", ptr(g), g.numel(), ptr(partials[offset:]) if count else ptr(partials), count, stream())
+
+
+def grad_clip_finalize(partials, n, max_norm, out, skipped=None):
+    """out fp32 [>= 3] = (total_norm, clip coefficient, 1 if finite else 0) from the first n partials; skipped (int32 [1] or None)
+    is incremented on the device when the norm is not finite.  max_norm None / <= 0 / inf: no clipping (coefficient exactly 1)."""
+    assert partials.dtype == torch.float64 and out.dtype == torch.float32 and out.numel() >= 3 and n <= partials.numel()
+    assert skipped is None or (skipped.dtype == torch.int32 and skipped.numel() >= 1)
+    _hip.require_gpu(partials, out, skipped)
+    call("mmg_grad_clip_finalize", ptr(partials), int(n), 0.0 if max_norm is None else float(max_norm), ptr(out), ptr(skipped), stream())
+
+
+def adamw_step_guarded(p, g, m, v, p16, lr, beta1, beta2, eps, wd, step, clip, skipped=None):
+    """adamw_step with the gradient scale (clip[1]), the go/no-go (clip[2]) and Adam's clock (step - skipped[0]) read on the device."""
+    assert clip.dtype == torch.float32 and clip.numel() >= 3 and (skipped is None or skipped.dtype == torch.int32)
+    call("mmg_adamw_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(beta1), float(beta2),
+         float(eps), float(wd), int(step), ptr(clip), ptr(skipped), stream())
+
+
 def dwconv_mfma_pays(n, H, W, C, flip):
     """Where the matrix-core kernel beats the VALU one in the same-process A/B (tools/dwm_scale.py at n = 256, tools/dwm_scale_b.py at n = 64;
     profiles/r04_dwconv_mfma_scale2.txt, _scale_b2.txt - after the kernel's loads were made unconditional and its spills removed: -25 % / -23 % at

@@ -14,18 +14,43 @@ State layout = torch.optim.AdamW's: `state[p] = {'step': fp32 0-d tensor, 'exp_a
 round-trip and are interchangeable with the reference's torch.optim.AdamW PROVIDED both list the same parameters in the same order:
 the reference passes `model.parameters()` - frozen BERT included - and so does ClassifierExperiment here (parameters without a
 gradient are skipped and get no state, as in torch).  For arena parameters `exp_avg` / `exp_avg_sq` are
-views into two flat buffers (rebuilt from the per-parameter tensors after a load)."""
+views into two flat buffers (rebuilt from the per-parameter tensors after a load).
+
+`max_grad_norm` / `skip_nonfinite` (additive; off by default, and then `step()` issues exactly the launches it always did): clip the
+gradients by their global L2 norm, as torch.nn.utils.clip_grad_norm_ over every gradient this optimizer applies, and leave
+parameters and moments untouched when that norm is NaN or Inf (csrc/grad_clip.hip).  `skip_nonfinite` defaults to True when
+`max_grad_norm` is given and to off when it is not; `skip_nonfinite=True` alone guards without clipping.  With
+`max_grad_norm` set and `skip_nonfinite=False` nothing is held back: a NaN norm gives a NaN coefficient, which the AdamW launches
+write into every parameter and moment - exactly what clip_grad_norm_ (error_if_nonfinite=False) followed by torch.optim.AdamW does.
+One exception to "reads nothing back": a state created AFTER guarded steps have run (a parameter unfrozen mid-run) reads the
+skipped count once, at that step, to start its counter there (`_new_counter`).  The norm, the coefficient, the decision and
+the count of skipped steps stay on the device: `step()` reads nothing back.  The host step counters keep counting `step()` calls;
+Adam's clock is `step - skipped` on the device, and `state_dict()` writes that difference, which is what torch.optim.AdamW would
+have written had the bad steps not been taken."""
+import math
+
 import torch
 
 from . import kernels as K
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, arenas=()):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, arenas=(), max_grad_norm=None,
+                 skip_nonfinite=None):
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
+            raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         # `arenas` is accepted for backward compatibility; arenas are discovered from the parameters at step time
         self._flat = {}              # id(arena) -> dict(arena, m, v, step)
+        self.max_grad_norm = None if max_grad_norm is None or math.isinf(float(max_grad_norm)) else float(max_grad_norm)
+        # skip_nonfinite=None: True beside a max_grad_norm, off without one - so that FusedAdamW(params, lr=...) stays the unguarded
+        # step, launch for launch, while skip_nonfinite=True on its own guards without clipping
+        self.skip_nonfinite = (max_grad_norm is not None) if skip_nonfinite is None else bool(skip_nonfinite)
+        self.grad_norm = None        # device fp32 [4] of the last guarded step: total norm, clip coefficient, 1 = finite, spare
+        self._skipped = None         # device int32 [1]: guarded steps that were not applied since the counters were last loaded
+        self._clock_running = False  # a guarded step has run since then (a state created later starts at the skipped count)
+        self._partials, self._piece_sizes, self._piece_counts = None, None, None
 
     # ---- state plumbing --------------------------------------------------------------------------------------------
     def _flat_state(self, arena):
@@ -37,7 +62,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if bound:
             return fs
         m, v = torch.zeros_like(arena.data), torch.zeros_like(arena.data)
-        step = torch.zeros((), dtype=torch.float32)
+        step = self._new_counter()
         for n, p in zip(arena.names, arena.params):
             o = arena.offsets[n]
             mv, vv = m[o:o + p.numel()].view(p.shape), v[o:o + p.numel()].view(p.shape)
@@ -55,16 +80,35 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         """torch.optim.AdamW's layout.  The parameters of an arena share ONE live step counter; a serialised state gets a counter
         of its own per parameter, as torch writes it (torch's foreach step increments every counter it is handed: a tensor listed
-        178 times would be incremented 178 times per step)."""
+        178 times would be incremented 178 times per step).  With the non-finite guard on, the counters are written minus the steps
+        that were skipped (one read-back): the checkpoint torch.optim.AdamW would have written, not having taken those steps."""
         sd = super().state_dict()
-        sd["state"] = {k: {kk: (vv.clone() if kk == "step" and torch.is_tensor(vv) else vv) for kk, vv in v.items()}
-                       for k, v in sd["state"].items()}
+        k = self.skipped_steps()
+        sd["state"] = {i: {kk: ((vv - k).clamp_(min=0) if k else vv.clone()) if kk == "step" and torch.is_tensor(vv) else vv
+                           for kk, vv in v.items()} for i, v in sd["state"].items()}
         return sd
+
+    def load_state_dict(self, state_dict):
+        """The loaded counters are Adam's clock itself: the device count of skipped steps starts again at zero."""
+        super().load_state_dict(state_dict)
+        if self._skipped is not None:
+            self._skipped.zero_()
+        self._clock_running = False
+
+    def skipped_steps(self):
+        """Guarded steps whose gradient norm was not finite and that were therefore not applied (one read-back, on request)."""
+        return int(self._skipped.item()) if self._skipped is not None else 0
+
+    def _new_counter(self):
+        """Step counter of a state created now.  Adam's clock is `step - skipped` with ONE device count of skipped steps, so a state that
+        joins after guarded steps have run (a parameter unfrozen mid-run) starts at that count - the only read-back `step()` can make,
+        and only at such a join."""
+        return torch.full((), float(self.skipped_steps() if self._clock_running else 0), dtype=torch.float32)
 
     def _tensor_state(self, p):
         st = self.state[p]
         if "exp_avg" not in st:
-            st["step"] = torch.zeros((), dtype=torch.float32)
+            st["step"] = self._new_counter()
             st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p.data), torch.zeros_like(p.data)
         elif not st["exp_avg"].is_contiguous() or st["exp_avg"].device != p.device:
             st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].to(p.device).contiguous(), st["exp_avg_sq"].to(p.device).contiguous()
@@ -73,11 +117,14 @@ class FusedAdamW(torch.optim.Optimizer):
         return st
 
     # ---- the step --------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _collect(self):
+        """Every update this step will make, each gradient exactly once: [(p, g, m, v, (lr, b1, b2, eps, wd), step)] - a whole arena
+        as ONE flat entry (its 64-element padding gaps are zero in the gradient and stay zero), anything else per tensor - and the
+        arenas that must be told their parameters moved.  Advances the host step counters; launches nothing but state set-up."""
+        jobs, touched = [], {}
         for group in self.param_groups:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+            hyper = (lr, b1, b2, eps, wd)
             in_group = {id(p) for p in group["params"]}
             arenas, done = {}, set()
             for p in group["params"]:
@@ -91,10 +138,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     continue
                 fs = self._flat_state(arena)
                 fs["step"] += 1
-                K.adamw_step(arena.data, arena.grad, fs["m"], fs["v"], None, lr, b1, b2, eps, wd, int(fs["step"]))
-                arena.touch()
+                jobs.append((arena.data, arena.grad, fs["m"], fs["v"], hyper, int(fs["step"])))
+                touched[id(arena)] = arena
                 done.update(id(p) for p in arena.params)
-            touched = {}
             for p in group["params"]:
                 if p.grad is None or id(p) in done:
                     continue
@@ -104,10 +150,45 @@ class FusedAdamW(torch.optim.Optimizer):
                 if st["step"].data_ptr() in {fs["step"].data_ptr() for fs in self._flat.values()}:
                     st["step"] = st["step"].clone()              # leaving the whole-arena path: own counter from here on
                 st["step"] += 1
-                K.adamw_step(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], None, lr, b1, b2, eps, wd, int(st["step"]))
+                jobs.append((p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], hyper, int(st["step"])))
                 a = getattr(p, "_mmg_arena", None)
-                if a is not None:
+                if a is not None:                # the update goes through a raw pointer: p._version does not move, say so
                     touched[id(a)] = a
-            for a in touched.values():       # the update went through a raw pointer: p._version did not move, say so here
-                a.touch()
+        return jobs, list(touched.values())
+
+    def _clip_state(self, grads):
+        """Global norm of `grads` -> self.grad_norm (device), skipped-step count (device): one streaming reduction per gradient into
+        one fp64 partials buffer, one finalize launch.  The buffers are cached and re-made when the gradients' sizes change."""
+        dev = grads[0].device
+        sizes = tuple(g.numel() for g in grads)
+        if self._piece_sizes != sizes or self._partials.device != dev:
+            self._piece_counts = [K.grad_sumsq_partials(n) for n in sizes]
+            self._partials = torch.empty(sum(self._piece_counts), device=dev, dtype=torch.float64)
+            self._piece_sizes = sizes
+        if self.grad_norm is None or self.grad_norm.device != dev:
+            self.grad_norm = torch.zeros(4, device=dev, dtype=torch.float32)
+            self._skipped = torch.zeros(1, device=dev, dtype=torch.int32) if self.skip_nonfinite else None
+        off = 0
+        for g, c in zip(grads, self._piece_counts):
+            K.grad_sumsq(g, self._partials, off, c)
+            off += c
+        K.grad_clip_finalize(self._partials, off, self.max_grad_norm, self.grad_norm, self._skipped)
+        self._clock_running = True
+        return self.grad_norm, self._skipped
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        jobs, touched = self._collect()
+        if guarded and jobs:
+            # no .item(), no .cpu(), no synchronisation: the coefficient, the go/no-go and Adam's clock are read by the AdamW launches
+            clip, skipped = self._clip_state([j[1] for j in jobs])
+            for p, g, m, v, hyper, t in jobs:
+                K.adamw_step_guarded(p, g, m, v, None, *hyper, t, clip, skipped)
+        else:
+            for p, g, m, v, hyper, t in jobs:
+                K.adamw_step(p, g, m, v, None, *hyper, t)
+        for a in touched:        # (on a skipped step too: harmless, the towers re-cast unchanged parameters)
+            a.touch()
         return loss
