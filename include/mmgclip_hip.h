@@ -361,13 +361,15 @@ int mmg_col2im_nhwc(const void* dcol, void* dx, int n, int H, int W, int C, int 
                     mmg_stream_t stream);
 /* nn.MaxPool2d(3, stride 2, padding 1) forward (encoder.py:107). */
 int mmg_maxpool3x3s2_nhwc(const void* x, void* y, int n, int H, int W, int C, mmg_stream_t stream);
-/* nn.BatchNorm2d on rows [M = n*H*W, C]: column sums of x and x^2 (fp32, accumulated; zero them first) ... */
-int mmg_bn_stats(const void* x, int M, int C, float* sum, float* sumsq, mmg_stream_t stream);
-/* ... -> mean / rstd and the fused affine (scale, shift).  train != 0: batch statistics (biased variance) and torch's
- * running-statistics update with `momentum` (unbiased variance); train == 0: the running statistics are used. */
-int mmg_bn_finalize(const float* sum, const float* sumsq, int M, int C, const float* gamma, const float* beta, float eps,
-                    float momentum, float* running_mean, float* running_var, int train, float* mean, float* rstd,
-                    float* scale, float* shift, mmg_stream_t stream);
+/* nn.BatchNorm2d on rows [M = n*H*W, C]: column sums of x and x^2 (fp64 [C] each, accumulated; zero them first).  fp64 because the
+ * variance is sumsq / M - mean^2: fp32 sums lose mean^2 / var of their precision, fp64 ones keep rstd and running_var at fp32. ... */
+int mmg_bn_stats_f64(const void* x, int M, int C, double* sum, double* sumsq, mmg_stream_t stream);
+/* ... -> mean / rstd and the fused affine (scale, shift), each formed in fp64 and rounded to fp32 once.  train != 0: batch statistics
+ * (biased variance) and torch's running-statistics update with `momentum` (unbiased variance; running_mean / running_var a nullable
+ * pair); train == 0: the running statistics are used and sum / sumsq may be NULL. */
+int mmg_bn_finalize_f64(const double* sum, const double* sumsq, int M, int C, const float* gamma, const float* beta, float eps,
+                        float momentum, float* running_mean, float* running_var, int train, float* mean, float* rstd,
+                        float* scale, float* shift, mmg_stream_t stream);
 /* y = x * scale[c] + shift[c] (+ residual) (ReLU when relu != 0): bn + the bottleneck's shortcut add + ReLU in one pass. */
 int mmg_bn_apply(const void* x, const float* scale, const float* shift, const void* residual, void* y, int M, int C, int relu,
                  mmg_stream_t stream);

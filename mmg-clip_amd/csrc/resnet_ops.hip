@@ -124,72 +124,91 @@ MMG_API int mmg_maxpool3x3s2_nhwc(const void* x, void* y, int n, int H, int W, i
 }
 
 // ---- batch norm ----------------------------------------------------------------------------------------------------------------------
-// column sums of x and x^2 over a slab of rows (fp32, accumulated with atomics; the caller zeroes sum / sumsq)
+// Column sums of x and x^2 over a slab of rows, in fp64 from the first addition to the last (the caller zeroes sum / sumsq).
+// The variance is formed as sumsq / M - mean^2, which cancels mean^2 / var of the sums' precision: with fp32 sums and fp32 atomics
+// a channel whose mean is 16 standard deviations away from zero lost rstd's third digit, and running_var (fp32 state that is
+// checkpointed) with it.  In fp64 the same formula keeps 2^-53 (1 + mean^2 / var), far below the fp32 the results are rounded to.
+// A workgroup sums its row phases through LDS in a fixed order and issues ONE atomic per column and sum (it was one per thread:
+// 256 / (C/8) times as many, all onto the same 2 C addresses).
 __global__ __launch_bounds__(256) void bn_stats_kernel(const bf16_t* __restrict__ x, int M, int C, int rows_per_block,
-                                                       float* __restrict__ sum, float* __restrict__ sumsq) {
+                                                       double* __restrict__ sum, double* __restrict__ sumsq) {
+    __shared__ double part[4096];          // [row phase][sum | sumsq][C]: lanes * 2 * C <= (256 / cvec) * 16 * cvec doubles
     const int cvec = C / 8;
     const int r0 = blockIdx.x * rows_per_block, r1 = min(r0 + rows_per_block, M);
     // thread = (column group cv of 8 channels, row phase sub); 256 / cvec threads share a column group (cvec <= 256)
     const int cv = threadIdx.x % cvec, lanes = 256 / cvec, sub = threadIdx.x / cvec;
-    if (sub >= lanes) return;
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r = r0 + sub; r < r1; r += lanes) {
-        const uint4 v = *reinterpret_cast<const uint4*>(x + (size_t)r * C + cv * 8);
-        const float f[8] = {bf2f_lo(v.x), bf2f_hi(v.x), bf2f_lo(v.y), bf2f_hi(v.y), bf2f_lo(v.z), bf2f_hi(v.z), bf2f_lo(v.w), bf2f_hi(v.w)};
+    if (sub < lanes) {
+        double s[8] = {0., 0., 0., 0., 0., 0., 0., 0.}, q[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+        for (int r = r0 + sub; r < r1; r += lanes) {
+            const uint4 v = *reinterpret_cast<const uint4*>(x + (size_t)r * C + cv * 8);
+            const float f[8] = {bf2f_lo(v.x), bf2f_hi(v.x), bf2f_lo(v.y), bf2f_hi(v.y), bf2f_lo(v.z), bf2f_hi(v.z), bf2f_lo(v.w), bf2f_hi(v.w)};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] += f[e]; q[e] = fmaf(f[e], f[e], q[e]); }
+            for (int e = 0; e < 8; ++e) { s[e] += (double)f[e]; q[e] += (double)(f[e] * f[e]); }      // a bf16 squared is exact in fp32
+        }
+        double* ps = part + (size_t)sub * 2 * C + cv * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { ps[e] = s[e]; ps[C + e] = q[e]; }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { atomicAdd(sum + cv * 8 + e, s[e]); atomicAdd(sumsq + cv * 8 + e, q[e]); }
+    __syncthreads();
+    for (int j = threadIdx.x; j < 2 * C; j += 256) {       // j < C: sum of column j; else sumsq of column j - C
+        double t = 0.;
+        for (int l = 0; l < lanes; ++l) t += part[(size_t)l * 2 * C + j];
+        unsafeAtomicAdd(j < C ? sum + j : sumsq + (j - C), t);      // global_atomic_add_f64
+    }
 }
 
-MMG_API int mmg_bn_stats(const void* x, int M, int C, float* sum, float* sumsq, hipStream_t stream) {
-    MMG_CHECK_ARG(x && sum && sumsq && M > 0 && C >= 8 && C % 8 == 0 && C <= 2048, "mmg_bn_stats: M=%d C=%d (C multiple of 8, <= 2048)", M, C);
+MMG_API int mmg_bn_stats_f64(const void* x, int M, int C, double* sum, double* sumsq, hipStream_t stream) {
+    MMG_CHECK_ARG(x && sum && sumsq && M > 0 && C >= 8 && C % 8 == 0 && C <= 2048, "mmg_bn_stats_f64: M=%d C=%d (C multiple of 8, <= 2048)", M, C);
+    MMG_CHECK_ARG(((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(sumsq)) & 7) == 0, "mmg_bn_stats_f64: sum / sumsq must be 8-byte aligned");
     int blocks = cdiv(M, 64);
     if (blocks > 1024) blocks = 1024;
     const int rpb = cdiv(M, blocks);
     blocks = cdiv(M, rpb);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, M, C, rpb, sum, sumsq);
-    MMG_LAUNCH_CHECK("mmg_bn_stats");
+    MMG_LAUNCH_CHECK("mmg_bn_stats_f64");
     return 0;
 }
 
 // train != 0: mean / biased variance of the batch from (sum, sumsq, M); running statistics updated as torch does
 // (running = (1 - momentum) running + momentum batch, unbiased variance).  train == 0: running statistics are used.
-// Outputs: mean, rstd (for the backward) and the fused affine y = x * scale + shift.
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ sum, const float* __restrict__ sumsq, int M, int C,
+// Outputs: mean, rstd (for the backward) and the fused affine y = x * scale + shift.  One thread per channel: the statistics are
+// formed in fp64 and every fp32 output is rounded once.
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ sum, const double* __restrict__ sumsq, int M, int C,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                           float momentum, float* __restrict__ running_mean,
                                                           float* __restrict__ running_var, int train, float* __restrict__ mean,
                                                           float* __restrict__ rstd, float* __restrict__ scale, float* __restrict__ shift) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    float mu, var;
+    double mu, var;
     if (train) {
         mu = sum[c] / M;
-        var = fmaxf(sumsq[c] / M - mu * mu, 0.f);
+        var = fmax(sumsq[c] / M - mu * mu, 0.);
         if (running_mean) {
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (M > 1 ? (float)M / (M - 1) : 1.f);
+            const double keep = 1. - (double)momentum;
+            running_mean[c] = (float)(keep * running_mean[c] + momentum * mu);
+            running_var[c] = (float)(keep * running_var[c] + momentum * var * (M > 1 ? (double)M / (M - 1) : 1.));
         }
     } else {
         mu = running_mean[c];
         var = running_var[c];
     }
-    const float rs = rsqrtf(var + eps);
-    mean[c] = mu; rstd[c] = rs;
+    const float rs = (float)(1. / sqrt(var + (double)eps));
+    const float mf = (float)mu;
+    mean[c] = mf; rstd[c] = rs;
     const float sc = gamma[c] * rs;
-    scale[c] = sc; shift[c] = beta[c] - mu * sc;
+    scale[c] = sc; shift[c] = beta[c] - mf * sc;
 }
 
-MMG_API int mmg_bn_finalize(const float* sum, const float* sumsq, int M, int C, const float* gamma, const float* beta, float eps,
-                            float momentum, float* running_mean, float* running_var, int train, float* mean, float* rstd,
-                            float* scale, float* shift, hipStream_t stream) {
-    MMG_CHECK_ARG(gamma && beta && mean && rstd && scale && shift && M > 0 && C > 0, "mmg_bn_finalize: bad argument");
-    MMG_CHECK_ARG(train ? (sum && sumsq) : (running_mean && running_var), "mmg_bn_finalize: missing statistics for this mode");
+MMG_API int mmg_bn_finalize_f64(const double* sum, const double* sumsq, int M, int C, const float* gamma, const float* beta, float eps,
+                                float momentum, float* running_mean, float* running_var, int train, float* mean, float* rstd,
+                                float* scale, float* shift, hipStream_t stream) {
+    MMG_CHECK_ARG(gamma && beta && mean && rstd && scale && shift && M > 0 && C > 0, "mmg_bn_finalize_f64: bad argument");
+    MMG_CHECK_ARG(train ? (sum && sumsq) : (running_mean && running_var), "mmg_bn_finalize_f64: missing statistics for this mode");
+    MMG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "mmg_bn_finalize_f64: running_mean and running_var go together");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, stream, sum, sumsq, M, C, gamma, beta, eps, momentum,
                        running_mean, running_var, train, mean, rstd, scale, shift);
-    MMG_LAUNCH_CHECK("mmg_bn_finalize");
+    MMG_LAUNCH_CHECK("mmg_bn_finalize_f64");
     return 0;
 }
 

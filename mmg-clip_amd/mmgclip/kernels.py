@@ -493,11 +493,11 @@ def batchnorm_fwd(x, gamma, beta, running_mean, running_var, train, eps=1e-5, mo
     """nn.BatchNorm2d on rows [M, C] (+ shortcut add + ReLU in the same pass) -> y, mean, rstd."""
     M, C = x.shape
     dev = x.device
-    st = torch.zeros(2, C, device=dev, dtype=torch.float32) if train else None
+    st = torch.zeros(2, C, device=dev, dtype=torch.float64) if train else None      # fp64 sums: var = sumsq / M - mean^2 cancels
     if train:
-        call("mmg_bn_stats", ptr(x), M, C, ptr(st[0]), ptr(st[1]), stream())
+        call("mmg_bn_stats_f64", ptr(x), M, C, ptr(st[0]), ptr(st[1]), stream())
     out4 = torch.empty(4, C, device=dev, dtype=torch.float32)          # mean, rstd, scale, shift
-    call("mmg_bn_finalize", ptr(st[0]) if train else None, ptr(st[1]) if train else None, M, C, ptr(gamma), ptr(beta), float(eps),
+    call("mmg_bn_finalize_f64", ptr(st[0]) if train else None, ptr(st[1]) if train else None, M, C, ptr(gamma), ptr(beta), float(eps),
          float(momentum), ptr(running_mean), ptr(running_var), 1 if train else 0, ptr(out4[0]), ptr(out4[1]), ptr(out4[2]),
          ptr(out4[3]), stream())
     y = torch.empty_like(x)
