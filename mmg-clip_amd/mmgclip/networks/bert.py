@@ -20,7 +20,8 @@ import torch.nn as nn
 from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
-from ..params import ParamArena, backward_finished, last_backward, note_forward, stream_anchor
+from ..params import backward_finished, last_backward
+from .tower import Tower
 
 
 class BertConfigLite:
@@ -78,7 +79,7 @@ def _hf_layout(cfg):
     return m
 
 
-class BertTower(nn.Module):
+class BertTower(Tower):
     def __init__(self, config=None, micro_batch=4096, dropout=True):
         super().__init__()
         self.config = config or BertConfigLite()
@@ -89,14 +90,9 @@ class BertTower(nn.Module):
         self.model_output_dimension = self.config.hidden_size
         self.micro_batch = micro_batch        # sequences per pass
         self.packed = os.environ.get("MMG_BERT_PACKED", "1") != "0"     # run the layers on the valid tokens only
-        self._arena = None
-        self._wc = None
-        self._wc_version = None
-        self._anchor = None
-        self.post_backward_hook = None      # called with the arena once this tower's gradients are complete
 
     # ---- parameter plumbing: arena order puts q,k,v (weights, then biases) of a layer next to each other -----
-    def _ordered_named_parameters(self):
+    def _arena_parameters(self):
         named = dict(self.model.named_parameters())
         order = [n for n in named if n.startswith("embeddings.")]
         for i in range(self.config.num_hidden_layers):
@@ -108,23 +104,8 @@ class BertTower(nn.Module):
         assert len(order) == len(named)
         return [(n, named[n]) for n in order]
 
-    def _materialize(self, device):
-        if self._arena is not None and self._arena.device == device and self._arena.is_bound():
-            return
-        self._arena = ParamArena(self._ordered_named_parameters(), device)
-        self._wc_version = None
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
-
-    @property
-    def arena(self):
-        return self._arena
-
-    def _refresh_working_copies(self):
-        A = self._arena
-        v = A.version()
-        if self._wc_version == v:
-            return
-        H = self.config.hidden_size
+    def _build_working_copies(self):
+        A, H = self._arena, self.config.hidden_size
         wc = {}
         e = self.model.embeddings
         wc["word"], wc["pos"], wc["type"] = (K.cast_bf16(e.word_embeddings.weight.data), K.cast_bf16(e.position_embeddings.weight.data),
@@ -138,9 +119,10 @@ class BertTower(nn.Module):
             for tag, lin in (("wo", lyr.attention.output.dense), ("wi", lyr.intermediate.dense), ("wf", lyr.output.dense)):
                 wc[f"{i}.{tag}"] = K.cast_bf16(lin.weight.data)
                 wc[f"{i}.{tag}t"] = K.transpose_cast_bf16(lin.weight.data)
-        self._wc, self._wc_version = wc, v
+        return wc
 
-    def _check_qkv_contiguous(self):
+    def _bound(self):
+        """The fused QKV GEMM reads q, k, v of a layer as one span of the arena: check the arena that was just built."""
         H = self.config.hidden_size
         A = self._arena
         assert (H * H) % 64 == 0 and H % 64 == 0, "fused QKV views need 64-element aligned slices"
@@ -367,18 +349,14 @@ class BertTower(nn.Module):
         packed=True (default: self.packed) computes the rows of valid tokens only and leaves zeros in the padding rows;
         packed=False reproduces HF's values there too."""
         _hip.require_gpu(input_ids)
-        self._materialize(input_ids.device)
-        self._check_qkv_contiguous()
         ids = input_ids.to(torch.int64).contiguous()
         mask = attention_mask.to(torch.int64).contiguous() if attention_mask is not None else None
         tt = token_type_ids.to(torch.int64).contiguous() if token_type_ids is not None else None
         if ids.shape[1] > self.config.max_position_embeddings:
             raise ValueError(f"sequence length {ids.shape[1]} exceeds max_position_embeddings")
-        needs_grad = torch.is_grad_enabled() and self._arena.any_trainable()
         use_packed = self.packed if packed is None else bool(packed)
         lens = self._lengths_of(attention_mask) if (use_packed and attention_mask is not None and ids.shape[1] <= 256) else None
-        note_forward(self, needs_grad)
-        return _BertFn.apply(self, ids, tt, mask, stream_anchor(self, self._anchor.device) if needs_grad else None, lens)
+        return _BertFn.apply(self, ids, tt, mask, self._record_forward(input_ids.device), lens)
 
 
 class _BertFn(torch.autograd.Function):

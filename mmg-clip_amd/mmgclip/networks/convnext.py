@@ -33,8 +33,9 @@ from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
 from .._hip import call, ptr, stream
-from ..params import ParamArena, backward_finished, last_backward, note_forward, stream_anchor
+from ..params import backward_finished, last_backward
 from .convnext_plan import BlockSaved, Knobs, decide_saves, fused_forward, plan_block, saving_form
+from .tower import Tower, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
 
 CONFIGS = {
     "tiny": dict(depths=(3, 3, 9, 3), dims=(96, 192, 384, 768)),
@@ -94,7 +95,7 @@ class _TorchvisionLayout(nn.Module):
         self.avgpool = nn.AdaptiveAvgPool2d(1)
 
 
-class ConvNextTower(nn.Module):
+class ConvNextTower(Tower):
     """pixels fp32 [n, Cin, H, W] in [0,1] (scale16=True applies the reference's 16-bit scaling) -> features [n, dims[-1]]."""
 
     def __init__(self, variant="tiny", in_chans=1, scale16=True, micro_batch=64, fused_mlp=None, checkpoint=False, fp8=False,
@@ -136,25 +137,11 @@ class ConvNextTower(nn.Module):
         self.model = _TorchvisionLayout(variant, in_chans)
         self.model_output_dimension = self.dims[-1]
         self.kp = (16 * in_chans + 31) // 32 * 32          # stem GEMM K padded to the MFMA k-step
-        self._arena = None
-        self._wc = None
-        self._wc_version = None
         self.plan = None                    # one BlockPlan per stage; made with the working copies (knobs may be set after construction)
-        self._anchor = None
-        self.post_backward_hook = None      # called with the arena once this tower's gradients are complete
 
     # ---- parameter plumbing ------------------------------------------------------------------------------
-    def _materialize(self, device):
-        if self._arena is not None and self._arena.device == device and self._arena.is_bound():
-            return
-        self._arena = ParamArena(list(self.model.named_parameters()), device)
-        self._wc_version = None
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
+    def _bound(self):
         self._pname = {id(m): "features." + n for n, m in self.model.features.named_modules()}
-
-    @property
-    def arena(self):
-        return self._arena
 
     def _g(self, mod, leaf):
         """Gradient view (arena) of parameter `leaf` of module `mod`."""
@@ -166,20 +153,12 @@ class ConvNextTower(nn.Module):
     def _plan_blocks(self):
         return tuple(plan_block(C, self.knobs()) for C in self.dims)
 
-    def _refresh_working_copies(self):
-        """bf16 / transposed / tap-major copies the kernels read; rebuilt only when a parameter changed.  Which copies a block gets follows
-        from its BlockPlan (self.plan, made here)."""
-        A = self._arena
-        v = A.version()
-        if self._wc_version == v:
-            return
+    def _build_working_copies(self):
+        """bf16 / transposed / tap-major copies the kernels read.  Which copies a block gets follows from its BlockPlan (self.plan, made
+        here)."""
         f = self.model.features
-        plan = self._plan_blocks()
-        wc = {}
-        stem = f[0][0].weight.data                                   # [C0, Cin, 4, 4] -> [(kh,kw,ci)] padded
-        w = torch.zeros(stem.shape[0], self.kp, device=stem.device)
-        w[:, :16 * self.in_chans] = stem.permute(0, 2, 3, 1).reshape(stem.shape[0], -1)
-        wc["stem.w"] = K.cast_bf16(w)
+        plan = self.plan = self._plan_blocks()
+        wc = {"stem.w": K.cast_bf16(conv_weight_rows(f[0][0].weight.data))}          # [C0, Cin, 4, 4] -> [C0, kp]
         for si, p in enumerate(plan):
             C = p.C
             for bi, blk in enumerate(f[1 + 2 * si]):
@@ -204,11 +183,10 @@ class ConvNextTower(nn.Module):
                         wc[key + ".bwdw"] = K.cnblock_bwdw_pack(w1, w2, blk.block[2].weight.data, blk.block[2].bias.data, gamma,
                                                                 blk.block[3].bias.data)
             if si < 3:
-                conv = f[2 + 2 * si][1].weight.data                                          # [2C, C, 2, 2]
-                wds = conv.permute(0, 2, 3, 1).reshape(conv.shape[0], -1).contiguous()       # [(kh,kw,ci)]
+                wds = conv_weight_rows(f[2 + 2 * si][1].weight.data)                         # [2C, C, 2, 2] -> [2C, 4C]: no padding
                 wc[f"ds{si}.w"] = K.cast_bf16(wds)
                 wc[f"ds{si}.wt"] = K.transpose_cast_bf16(wds)
-        self._wc, self._wc_version, self.plan = wc, v, plan
+        return wc
 
     def _decide_saves(self, n_alive, H, W, device, ckpt=False, more=()):
         """-> SaveDecision of a forward whose saved tensors of n_alive H x W images (and of `more`: further (n, H, W) triples, a batch of several
@@ -387,8 +365,8 @@ class ConvNextTower(nn.Module):
         p0, s0, mean, rstd = saved["stem"]
         ds0 = K.layernorm_bwd(dx, s0, mean, rstd, f[0][1].weight.data, self._g(f[0][1], "weight"), self._g(f[0][1], "bias"))
         L.gemm_tn_acc(ds0, p0, tmp["stem.dw"], colsum=self._g(f[0][0], "bias"))
-        if final:
-            self._finalize_stem(tmp)
+        if final:                           # fold the GEMM-shaped stem temporary ([C0, kp], zero-padded tail) into the torch-layout gradient
+            fold_conv_grad(tmp["stem.dw"], self._g(f[0][0], "weight"), self.dims[0], self.in_chans, 4, 4)
 
     def _alloc_tmp(self, device):
         z = lambda *s: torch.zeros(*s, device=device, dtype=torch.float32)   # noqa: E731
@@ -401,14 +379,6 @@ class ConvNextTower(nn.Module):
             if si < 3:
                 tmp[f"ds{si}.dw"] = z(self.dims[si + 1], 4 * C)
         return tmp
-
-    def _finalize_stem(self, tmp):
-        """Fold the GEMM-shaped stem temporary into the torch-layout gradient."""
-        # the stem temp is [C0, Kp] with zero-padded tail columns: relayout the first 16*Cin columns
-        kk = 16 * self.in_chans
-        src = tmp["stem.dw"][:, :kk].contiguous()
-        call("mmg_grad_relayout", ptr(src), ptr(self._g(self.model.features[0][0], "weight")), 0, self.dims[0], self.in_chans, 4, 4, kk,
-             stream())
 
     def _finalize_stage(self, tmp, si):
         """Fold stage si's GEMM-shaped temporaries (and those of the downsample layer behind it) into the torch-layout gradients
@@ -424,9 +394,7 @@ class ConvNextTower(nn.Module):
             call("mmg_grad_relayout", ptr(tmp[key + ".dw49"]), ptr(self._g(blk.block[0], "weight")), 1, C, 1, 7, 7, C,
                  stream())
         if si < 3:
-            conv = f[2 + 2 * si][1]
-            call("mmg_grad_relayout", ptr(tmp[f"ds{si}.dw"]), ptr(self._g(conv, "weight")), 0, self.dims[si + 1], C, 2, 2,
-                 4 * C, stream())
+            fold_conv_grad(tmp[f"ds{si}.dw"], self._g(f[2 + 2 * si][1], "weight"), self.dims[si + 1], C, 2, 2)
 
     # ---- public -----------------------------------------------------------------------------------------------
     def feature_map_shape(self, H, W):
@@ -454,10 +422,7 @@ class ConvNextTower(nn.Module):
             if images.shape[-2] < 32 or images.shape[-1] < 32:
                 raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(images.shape)}")
             device = images.device
-        self._materialize(device)
-        needs_grad = torch.is_grad_enabled() and self._arena.any_trainable()
-        note_forward(self, needs_grad)
-        anchor = stream_anchor(self, self._anchor.device) if needs_grad else None
+        anchor = self._record_forward(device)
         if plan is None:
             return _ConvNextFn.apply(self, images.float().contiguous(), anchor, None)
         return _ConvNextFn.apply(self, [t.float() for t in images], anchor, plan)
@@ -485,7 +450,6 @@ class _ConvNextFn(torch.autograd.Function):
     def forward(ctx, tower, images, anchor, plan):
         tower._refresh_working_copies()
         save = anchor is not None
-        feats, saved = [], []
         mb = tower.micro_batch
         ckpt = save and tower.checkpoint
         if plan is None:
@@ -510,21 +474,10 @@ class _ConvNextFn(torch.autograd.Function):
         if save:
             dec = tower._decide_saves(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
             tower.save_ln, tower.save_gelu, tower.fp8_bwd_now = dec         # (the latest forward's, for whoever reports them: bench.py)
-        for k, part in enumerate(parts):
-            # gradient checkpointing at micro-batch granularity: keep only the pixels, re-run the micro-batch's forward (with its
-            # activations saved) right before its backward - activation memory becomes one micro-batch instead of the whole batch.
-            # The LAST micro-batch keeps its activations (round 4): the backward starts with it (reverse order), so still only one
-            # micro-batch's activations are alive at any time, and one of the n recomputations is not run (MMG_CKPT_KEEP_LAST=0: all are).
-            keep = ckpt and k == len(parts) - 1 and os.environ.get("MMG_CKPT_KEEP_LAST", "1") != "0"
-            pix = part()
-            ft, sv = tower._forward_mb(pix, blocks, dec if (not ckpt or keep) else None)
-            feats.append(ft)
-            saved.append({"recompute": part, "n": pix.shape[0]} if (ckpt and not keep) else sv)     # (the pixels are sliced / stacked again then)
-            del pix
-        ctx.tower, ctx.saved_mb, ctx.reverse = tower, saved if save else None, ckpt
+        out, parts = forward_parts(parts, lambda pix, saving: tower._forward_mb(pix, blocks, dec if saving else None), ckpt)
+        ctx.tower, ctx.parts = tower, parts if save else None
         ctx.plan, ctx.decision = blocks, dec
         ctx.inverse = None
-        out = torch.cat(feats, 0) if len(feats) > 1 else feats[0]
         if plan is not None and plan[1] != list(range(count)):
             ctx.inverse = torch.tensor(plan[1], device=device)
             out = out.index_select(0, ctx.inverse)             # processing order -> input order
@@ -538,20 +491,9 @@ class _ConvNextFn(torch.autograd.Function):
         dfeat = dfeat.float().contiguous()
         if ctx.inverse is not None:                                # input order -> processing order
             dfeat = torch.empty_like(dfeat).index_copy_(0, ctx.inverse, dfeat)
-        sizes = [sv["n"] if "recompute" in sv else sv["shape"][0] for sv in ctx.saved_mb]
-        starts = [sum(sizes[:k]) for k in range(len(sizes))]
-        order = list(range(len(sizes)))
-        if ctx.reverse:                      # checkpointing: the micro-batch whose activations were kept (the last one) first
-            order.reverse()
-        for pos, k in enumerate(order):
-            sv = ctx.saved_mb[k]
-            if "recompute" in sv:
-                _, sv = tower._forward_mb(sv["recompute"](), ctx.plan, ctx.decision)
-            i, n = starts[k], sizes[k]
-            final = pos == len(order) - 1
-            tower._backward_mb(dfeat[i:i + n].contiguous(), sv, tmp, final=final, announce=final and last_backward(tower))
-            sv.clear()
-            ctx.saved_mb[k] = None
-        ctx.saved_mb = None
+
+        def bwd(d, saved, final):            # final: the GEMM-shaped temporaries are folded, and (the step's last backward) announced
+            tower._backward_mb(d, saved, tmp, final=final, announce=final and last_backward(tower))
+        backward_parts(ctx.parts, dfeat, lambda pix: tower._forward_mb(pix, ctx.plan, ctx.decision)[1], bwd)
         backward_finished(tower)
         return None, None, None, None

@@ -17,8 +17,8 @@ import torch.nn as nn
 from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
-from ..params import ParamArena, backward_finished, note_forward, stream_anchor
-from .._hip import call, ptr, stream
+from ..params import backward_finished
+from .tower import Tower, conv_weight_rows, fold_conv_grad
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 LAYERS = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))       # (width, blocks, stride of the first block)
@@ -57,7 +57,7 @@ class _TorchvisionResNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
 
-class ResNetTower(nn.Module):
+class ResNetTower(Tower):
     def __init__(self):
         super().__init__()
         self.model = _TorchvisionResNet()
@@ -66,42 +66,21 @@ class ResNetTower(nn.Module):
             p.requires_grad = False
         for p in self.model.layer4.parameters():
             p.requires_grad = True
-        self._arena = None
-        self._wc, self._wc_version = None, None
-        self._anchor = None
-        self.post_backward_hook = None
 
     # ---- parameters -----------------------------------------------------------------------------------------------------
-    @property
-    def arena(self):
-        return self._arena
+    def _arena_parameters(self):
+        """The trainable part: one buffer, one AdamW launch, one all-reduce."""
+        return [("layer4." + n, p) for n, p in self.model.layer4.named_parameters()]
 
-    def _materialize(self, device):
-        if self._arena is not None and self._arena.device == device and self._arena.is_bound():
-            return
-        named = [("layer4." + n, p) for n, p in self.model.layer4.named_parameters()]
-        self._arena = ParamArena(named, device)           # the trainable part: one buffer, one AdamW launch, one all-reduce
-        self._wc_version = None
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
+    def _working_copy_key(self):
+        return (self._arena.version(), sum(p._version for p in self.model.parameters()))        # + the frozen layers, outside the arena
 
     @staticmethod
     def _w2d(conv, cin_pad=None):
-        """[Cout, Cin, kh, kw] -> [Cout, (kh, kw, ci)] fp32 (input channels zero-padded to cin_pad), K padded to 32."""
-        w = conv.weight.data
-        co, ci, kh, kw = w.shape
-        if cin_pad and cin_pad > ci:
-            w = torch.cat([w, torch.zeros(co, cin_pad - ci, kh, kw, device=w.device)], 1)
-            ci = cin_pad
-        w = w.permute(0, 2, 3, 1).reshape(co, kh * kw * ci)
-        kp = (w.shape[1] + 31) // 32 * 32
-        if kp != w.shape[1]:
-            w = torch.cat([w, torch.zeros(co, kp - w.shape[1], device=w.device)], 1)
-        return w.contiguous()
+        """A convolution's weight as the GEMM rows its im2col'd input meets (tests read the stem's padded K from here)."""
+        return conv_weight_rows(conv.weight.data, cin_pad)
 
-    def _refresh_working_copies(self):
-        v = (self._arena.version(), sum(p._version for p in self.model.parameters()))
-        if self._wc_version == v:
-            return
+    def _build_working_copies(self):
         wc = {"conv1": K.cast_bf16(self._w2d(self.model.conv1, 8))}
         for li in range(4):
             for bi, blk in enumerate(getattr(self.model, f"layer{li + 1}")):
@@ -113,7 +92,7 @@ class ResNetTower(nn.Module):
                         wc[key + name + "t"] = K.transpose_cast_bf16(w2)
                 if blk.downsample is not None:
                     wc[key + "ds"] = K.cast_bf16(self._w2d(blk.downsample[0]))
-        self._wc, self._wc_version = wc, v
+        return wc
 
     # ---- pieces -----------------------------------------------------------------------------------------------------------
     def _bn(self, x, bn, residual=None, relu=True):
@@ -163,7 +142,7 @@ class ResNetTower(nn.Module):
         tmp = torch.zeros(width, 9 * width, device=dout.device, dtype=torch.float32)
         L.gemm_tn_acc(dx2, col2, tmp)
         del col2
-        call("mmg_grad_relayout", ptr(tmp), ptr(g("conv2.weight")), 0, width, width, 3, 3, 9 * width, stream())
+        fold_conv_grad(tmp, g("conv2.weight"), width, width, 3, 3)
         dcol = L.gemm_nt(dx2, wc[key + "conv2t"])
         del dx2
         da1 = K.col2im(dcol, n, H, W, width, 3, s, 1)
@@ -209,10 +188,7 @@ class ResNetTower(nn.Module):
         _hip.require_gpu(x)
         if x.dim() == 2:                                   # encoder.py:101-103
             x = x.view(x.shape[0], 1, 1, x.shape[1]).repeat(1, 3, 1, 1)
-        self._materialize(x.device)
-        needs_grad = torch.is_grad_enabled() and self.training and self._arena.any_trainable()
-        note_forward(self, needs_grad)
-        return _ResNetFn.apply(self, x.float().contiguous(), stream_anchor(self, self._anchor.device) if needs_grad else None)
+        return _ResNetFn.apply(self, x.float().contiguous(), self._record_forward(x.device, wants_grad=self.training))
 
 
 class _ResNetFn(torch.autograd.Function):

@@ -10,8 +10,6 @@ All layers reuse the BERT/ConvNeXt kernels: the 16x16/16 patch convolution is `m
 `mmg_attention_fwd/bwd` without a key mask (whole sequence in LDS) up to S = 256 tokens (224x224 -> 197) and the
 flash-style tiled `mmg_attention_long_fwd/bwd` beyond (1024x1024 -> S = 4097, BASELINE config C4).
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -19,7 +17,8 @@ from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
 from .._hip import call, ptr, stream
-from ..params import ParamArena, backward_finished, note_forward, stream_anchor
+from ..params import backward_finished
+from .tower import Tower, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
 
 LN_EPS = 1e-6
 
@@ -54,7 +53,7 @@ def _tv_layout(image_size, in_chans, hidden, layers, mlp_dim, patch):
     return m
 
 
-class ViTTower(nn.Module):
+class ViTTower(Tower):
     """pixels fp32 [n, Cin, H, W] -> class-token features [n, hidden]."""
 
     def __init__(self, image_size=224, in_chans=1, hidden=768, layers=12, heads=12, mlp_dim=3072, patch=16, scale16=True,
@@ -68,33 +67,12 @@ class ViTTower(nn.Module):
         self.model = _tv_layout(image_size, in_chans, hidden, layers, mlp_dim, patch)
         self.model_output_dimension = hidden
         self.kp = (patch * patch * in_chans + 31) // 32 * 32
-        self._arena = self._wc = self._wc_version = self._anchor = None
-        self.post_backward_hook = None
 
     def _blk(self, i):
         return getattr(self.model.encoder.layers, f"encoder_layer_{i}")
 
-    def _materialize(self, device):
-        if self._arena is not None and self._arena.device == device and self._arena.is_bound():
-            return
-        self._arena = ParamArena(list(self.model.named_parameters()), device)
-        self._wc_version = None
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
-
-    @property
-    def arena(self):
-        return self._arena
-
-    def _refresh_working_copies(self):
-        A = self._arena
-        v = A.version()
-        if self._wc_version == v:
-            return
-        wc = {}
-        cw = self.model.conv_proj.weight.data
-        w = torch.zeros(cw.shape[0], self.kp, device=cw.device)
-        w[:, :self.patch * self.patch * self.in_chans] = cw.permute(0, 2, 3, 1).reshape(cw.shape[0], -1)
-        wc["conv"] = K.cast_bf16(w)
+    def _build_working_copies(self):
+        wc = {"conv": K.cast_bf16(conv_weight_rows(self.model.conv_proj.weight.data))}       # [hidden, kp]
         wc["cls"] = K.cast_bf16(self.model.class_token.data.reshape(-1))
         wc["pos"] = K.cast_bf16(self.model.encoder.pos_embedding.data.reshape(self.seq, self.hidden))
         for i in range(self.layers):
@@ -103,7 +81,7 @@ class ViTTower(nn.Module):
                             ("f1", b.mlp[0].weight.data), ("f2", b.mlp[3].weight.data)):
                 wc[f"{i}.{tag}"] = K.cast_bf16(wt)
                 wc[f"{i}.{tag}t"] = K.transpose_cast_bf16(wt)
-        self._wc, self._wc_version = wc, v
+        return wc
 
     def _forward_mb(self, img, save):
         wc, H, S, heads = self._wc, self.hidden, self.seq, self.heads
@@ -179,18 +157,13 @@ class ViTTower(nn.Module):
         call("mmg_vit_assemble_bwd", ptr(dx), ptr(dtok), ptr(A.g("encoder.pos_embedding")), ptr(A.g("class_token")), B, S, H, stream())
         tmp = torch.zeros(H, self.kp, device=dx.device, dtype=torch.float32)
         L.gemm_tn_acc(dtok, saved["p0"], tmp, colsum=A.g("conv_proj.bias"))
-        kk = self.patch * self.patch * self.in_chans
-        src = tmp[:, :kk].contiguous()
-        call("mmg_grad_relayout", ptr(src), ptr(A.g("conv_proj.weight")), 0, H, self.in_chans, self.patch, self.patch, kk, stream())
+        fold_conv_grad(tmp, A.g("conv_proj.weight"), H, self.in_chans, self.patch, self.patch)
 
     def forward(self, images):
         _hip.require_gpu(images)
         if images.shape[-1] != self.image_size or images.shape[-2] != self.image_size:
             raise ValueError(f"ViT was built for {self.image_size}x{self.image_size} inputs (learned positions), got {tuple(images.shape)}")
-        self._materialize(images.device)
-        needs_grad = torch.is_grad_enabled() and self._arena.any_trainable()
-        note_forward(self, needs_grad)
-        return _ViTFn.apply(self, images.float().contiguous(), stream_anchor(self, self._anchor.device) if needs_grad else None)
+        return _ViTFn.apply(self, images.float().contiguous(), self._record_forward(images.device))
 
 
 class _ViTFn(torch.autograd.Function):
@@ -198,34 +171,17 @@ class _ViTFn(torch.autograd.Function):
     def forward(ctx, tower, images, anchor):
         tower._refresh_working_copies()
         save = anchor is not None
-        ckpt = save and tower.checkpoint
-        feats, saved = [], []
-        for i in range(0, images.shape[0], tower.micro_batch):
-            # (the last micro-batch keeps its activations and is the first one the backward takes: one recomputation less, still one
-            #  micro-batch of activations alive at a time - MMG_CKPT_KEEP_LAST=0 recomputes all)
-            keep = ckpt and i + tower.micro_batch >= images.shape[0] and os.environ.get("MMG_CKPT_KEEP_LAST", "1") != "0"
-            ft, sv = tower._forward_mb(images[i:i + tower.micro_batch], save and (not ckpt or keep))
-            feats.append(ft)
-            saved.append({"recompute": images[i:i + tower.micro_batch], "B": ft.shape[0]} if (ckpt and not keep) else sv)
-        ctx.tower, ctx.saved_mb, ctx.reverse = tower, saved if save else None, ckpt
-        return torch.cat(feats, 0) if len(feats) > 1 else feats[0]
+        mb = tower.micro_batch
+        parts = [(lambda i=i: images[i:i + mb]) for i in range(0, images.shape[0], mb)]
+        out, parts = forward_parts(parts, lambda pix, saving: tower._forward_mb(pix, save and saving), save and tower.checkpoint)
+        ctx.tower, ctx.parts = tower, parts if save else None
+        return out
 
     @staticmethod
     def backward(ctx, dfeat):
         tower = ctx.tower
         tower._arena.prepare_grads()
         dfeat = dfeat.float().contiguous()
-        sizes = [sv["B"] for sv in ctx.saved_mb]
-        starts = [sum(sizes[:k]) for k in range(len(sizes))]
-        order = list(range(len(sizes)))
-        if ctx.reverse:
-            order.reverse()
-        for k in order:
-            sv = ctx.saved_mb[k]
-            if "recompute" in sv:
-                _, sv = tower._forward_mb(sv["recompute"], True)
-            tower._backward_mb(dfeat[starts[k]:starts[k] + sizes[k]].contiguous(), sv)
-            ctx.saved_mb[k] = None
-        ctx.saved_mb = None
+        backward_parts(ctx.parts, dfeat, lambda pix: tower._forward_mb(pix, True)[1], lambda d, saved, last: tower._backward_mb(d, saved))
         backward_finished(tower)
         return None, None, None

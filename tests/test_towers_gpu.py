@@ -309,26 +309,29 @@ def test_vit_tower_forward_backward(dev):
     assert not bad, f"{len(bad)} gradients off: {list(bad.items())[:8]}"
 
 
-def test_vit_gradient_checkpointing_equals_plain_backward(dev):
+def test_vit_gradient_checkpointing_equals_plain_backward(dev, monkeypatch):
     """checkpoint=True keeps only the pixels of a micro-batch and re-runs its forward in the backward: same features and
-    (deterministic kernels, one writer per row) the same gradients as the saving path."""
+    (deterministic kernels, one writer per row) the same gradients as the saving path - with the last micro-batch's activations kept
+    (MMG_CKPT_KEEP_LAST=1, the default) and with every micro-batch recomputed (=0)."""
     from mmgclip.networks.encoder import ViTB16Encoder
     img = torch.rand(4, 1, 96, 96, generator=torch.Generator().manual_seed(1)).to(dev)
     wgt = torch.randn(4, 768, generator=torch.Generator().manual_seed(2)).to(dev)
     ref = ViTB16Encoder(image_size=96, layers=2, micro_batch=2)
     _randomize(ref, 3)
     out = {}
-    for ck in (False, True):
-        tower = ViTB16Encoder(image_size=96, layers=2, micro_batch=2, checkpoint=ck)
+    for ck in (False, "1", "0"):
+        monkeypatch.setenv("MMG_CKPT_KEEP_LAST", ck or "1")
+        tower = ViTB16Encoder(image_size=96, layers=2, micro_batch=2, checkpoint=bool(ck))
         tower.load_state_dict(ref.state_dict())
         tower = tower.to(dev)
         feat = tower(img)
         (feat * wgt).sum().backward()
         out[ck] = (feat.detach().clone(), {n: p.grad.detach().clone() for n, p in tower.model.named_parameters()})
-    assert torch.equal(out[True][0], out[False][0])
-    for n, gr in out[False][1].items():
-        rel = float((out[True][1][n] - gr).norm() / (gr.norm() + 1e-30))
-        assert rel < 1e-5, (n, rel)          # weight-gradient GEMMs accumulate with fp32 atomics: order noise only
+    for ck in ("1", "0"):
+        assert torch.equal(out[ck][0], out[False][0]), ck
+        for n, gr in out[False][1].items():
+            rel = float((out[ck][1][n] - gr).norm() / (gr.norm() + 1e-30))
+            assert rel < 1e-5, (ck, n, rel)          # weight-gradient GEMMs accumulate with fp32 atomics: order noise only
 
 
 def test_vit_tower_long_sequence_path(dev):
