@@ -385,34 +385,84 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttArgs a) {
     }
 }
 
-static int att_check(const char* who, int B, int S, int heads, int Hd, int ld, int smax) {
-    MMG_CHECK_ARG(B > 0 && S > 0 && S <= smax, "%s: S=%d must be in [1,%d]", who, S, smax);
-    MMG_CHECK_ARG(heads > 0 && Hd == heads * ATT_D, "%s: hidden=%d must equal heads=%d x 64", who, Hd, heads);
-    MMG_CHECK_ARG(ld >= 3 * Hd && ld % 8 == 0, "%s: qkv leading dimension %d", who, ld);
+// Host side.  Every entry point describes its call to att_args(), which does ALL the validation (before the first HIP call and before
+// any getenv) and fills AttArgs, then hands the arguments to the launcher of its kernel family.
+
+// what a backward needs on top of the forward's operands (ctx and lse become inputs); delta_ws: tiled kernels only
+struct AttBwdOps { const void* dctx; int lddc; void* dqkv; int lddq; float* delta_ws; };
+struct AttDropout { float p; unsigned long long seed; unsigned site; int first_sequence; };
+
+static int att_operand(const char* who, const char* name, const void* p, const char* ldname, int ld, int ld_min) {
+    MMG_CHECK_ARG(p, "%s: %s is null", who, name);
+    MMG_CHECK_ARG(ld >= ld_min && ld % 8 == 0, "%s: leading dimension %s=%d must be a multiple of 8 and >= %d", who, ldname, ld, ld_min);
     return 0;
 }
 
-// ctx = softmax(Q K^T * scale + key_mask) V per head; lse (nullable) receives the row log-sum-exp for the backward.
-MMG_API int mmg_attention_fwd(const void* qkv, int ld, const long long* mask, void* ctx, int ldc, float* lse, int B, int S,
-                              int heads, int Hd, float scale, hipStream_t stream) {
-    if (att_check("mmg_attention_fwd", B, S, heads, Hd, ld, 512)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && ldc >= Hd && ldc % 8 == 0, "mmg_attention_fwd: bad ctx");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = lse;
+// who: the entry point (first word of every message).  smax: the S limit of the kernel family.  flags: ATT_TILED = the flash-style kernels (1-D grid
+// of B * heads * blocks, delta_ws required in the backward), ATT_PACKED = cu_seqlens required.  bwd / drop: null for a forward / without dropout.
+enum { ATT_TILED = 1, ATT_PACKED = 2 };
+static int att_args(AttArgs& a, const char* who, int smax, int flags, const void* qkv, int ld, const long long* mask,
+                    const int* cu, const void* ctx, int ldc, const float* lse, int B, int S, int heads, int Hd, float scale,
+                    const AttBwdOps* bwd = nullptr, const AttDropout* drop = nullptr) {
+    const bool tiled = flags & ATT_TILED, packed = flags & ATT_PACKED;
+    MMG_CHECK_ARG(B > 0, "%s: B=%d must be positive", who, B);
+    MMG_CHECK_ARG(S > 0 && S <= smax, "%s: S=%d must be in [1,%d]", who, S, smax);
+    MMG_CHECK_ARG(heads > 0 && Hd == heads * ATT_D, "%s: hidden=%d must equal heads=%d x 64", who, Hd, heads);
+    MMG_CHECK_ARG(!tiled || (long)B * heads <= 0x7fffffffL, "%s: B=%d x heads=%d does not fit the grid", who, B, heads);
+    MMG_CHECK_ARG(!packed || cu, "%s: cu_seqlens is null", who);
+    if (att_operand(who, "qkv", qkv, "ld", ld, 3 * Hd) || att_operand(who, "ctx", ctx, "ldc", ldc, Hd)) return 1;
+    a = {};
+    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.cu = cu; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = const_cast<float*>(lse);
     a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
+    a.nbh = (int)((long)B * heads);
+    if (bwd) {
+        MMG_CHECK_ARG(lse, "%s: lse is null", who);
+        if (att_operand(who, "dctx", bwd->dctx, "lddc", bwd->lddc, Hd) || att_operand(who, "dqkv", bwd->dqkv, "lddq", bwd->lddq, 3 * Hd)) return 1;
+        MMG_CHECK_ARG(!tiled || bwd->delta_ws, "%s: delta_ws is null", who);
+        a.dctx = (const bf16_t*)bwd->dctx; a.lddc = bwd->lddc; a.dqkv = (bf16_t*)bwd->dqkv; a.lddq = bwd->lddq;
+    }
+    if (drop) {
+        MMG_CHECK_ARG(drop->p >= 0.f && drop->p < 1.f, "%s: dropout probability p=%g must be in [0, 1)", who, (double)drop->p);
+        MMG_CHECK_ARG(drop->first_sequence >= 0, "%s: first_sequence=%d must not be negative", who, drop->first_sequence);
+        a.drop.key = mmg_drop_key(drop->seed, drop->site);
+        a.drop.thresh = mmg_drop_threshold(drop->p);
+        a.drop.scale = 1.0f / (1.0f - drop->p);
+        a.bh0 = drop->first_sequence * heads;
+    }
+    return 0;
+}
+
+// whole-sequence forward: K and V images plus the additive key mask in LDS, NT = score tiles held in registers
+template <bool DROP>
+static void att_launch_fwd(const AttArgs& a, hipStream_t stream) {
     const size_t shm = (size_t)2 * a.S_pad * 128 + a.S_pad * 4;
-    const dim3 grid(B * heads);
     const int nt = a.S_pad / 16;
-#define ATT_FWD(NT)                                                                                   \
-    do {                                                                                              \
-        mmg_allow_lds(attn_fwd_kernel<NT, false>, shm);                                               \
-        hipLaunchKernelGGL((attn_fwd_kernel<NT, false>), grid, dim3(256), shm, stream, a);            \
+#define ATT_FWD(NT)                                                                                          \
+    do {                                                                                                     \
+        mmg_allow_lds(attn_fwd_kernel<NT, DROP>, shm);                                                       \
+        hipLaunchKernelGGL((attn_fwd_kernel<NT, DROP>), dim3(a.nbh), dim3(256), shm, stream, a);             \
     } while (0)
     if (nt <= 6) ATT_FWD(6);
     else if (nt <= 8) ATT_FWD(8);
     else if (nt <= 16) ATT_FWD(16);
     else ATT_FWD(32);
 #undef ATT_FWD
+}
+
+// whole-sequence backward: Q, K, V, dO images plus mask, lse and delta rows in LDS
+template <bool DROP>
+static void att_launch_bwd(const AttArgs& a, hipStream_t stream) {
+    const size_t shm = (size_t)4 * a.S_pad * 128 + 3 * a.S_pad * 4;
+    mmg_allow_lds(attn_bwd_kernel<DROP>, shm);
+    hipLaunchKernelGGL(attn_bwd_kernel<DROP>, dim3(a.nbh), dim3(256), shm, stream, a);
+}
+
+// ctx = softmax(Q K^T * scale + key_mask) V per head; lse (nullable) receives the row log-sum-exp for the backward.
+MMG_API int mmg_attention_fwd(const void* qkv, int ld, const long long* mask, void* ctx, int ldc, float* lse, int B, int S,
+                              int heads, int Hd, float scale, hipStream_t stream) {
+    AttArgs a;
+    if (att_args(a, "mmg_attention_fwd", 512, 0, qkv, ld, mask, nullptr, ctx, ldc, lse, B, S, heads, Hd, scale)) return 1;
+    att_launch_fwd<false>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_fwd");
     return 0;
 }
@@ -421,16 +471,10 @@ MMG_API int mmg_attention_fwd(const void* qkv, int ld, const long long* mask, vo
 MMG_API int mmg_attention_bwd(const void* qkv, int ld, const long long* mask, const void* ctx, int ldc, const float* lse,
                               const void* dctx, int lddc, void* dqkv, int lddq, int B, int S, int heads, int Hd, float scale,
                               hipStream_t stream) {
-    if (att_check("mmg_attention_bwd", B, S, heads, Hd, ld, 256)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && ldc >= Hd && lddc >= Hd && lddq >= 3 * Hd && ldc % 8 == 0 &&
-                      lddc % 8 == 0 && lddq % 8 == 0, "mmg_attention_bwd: bad pointer or leading dimension");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = const_cast<float*>(lse);
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    a.dctx = (const bf16_t*)dctx; a.lddc = lddc; a.dqkv = (bf16_t*)dqkv; a.lddq = lddq;
-    const size_t shm = (size_t)4 * a.S_pad * 128 + 3 * a.S_pad * 4;
-    mmg_allow_lds(attn_bwd_kernel<false>, shm);
-    hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(B * heads), dim3(256), shm, stream, a);
+    AttArgs a;
+    const AttBwdOps bwd = {dctx, lddc, dqkv, lddq, nullptr};
+    if (att_args(a, "mmg_attention_bwd", 256, 0, qkv, ld, mask, nullptr, ctx, ldc, lse, B, S, heads, Hd, scale, &bwd)) return 1;
+    att_launch_bwd<false>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_bwd");
     return 0;
 }
@@ -441,24 +485,9 @@ MMG_API int mmg_attention_bwd(const void* qkv, int ld, const long long* mask, co
 // (mmgclip_model.py:110-111), so the padded rows are pure overhead for the tower.
 MMG_API int mmg_attention_varlen_fwd(const void* qkv, int ld, const int* cu_seqlens, void* ctx, int ldc, float* lse, int B,
                                      int S_max, int heads, int Hd, float scale, hipStream_t stream) {
-    if (att_check("mmg_attention_varlen_fwd", B, S_max, heads, Hd, ld, 512)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && cu_seqlens && ldc >= Hd && ldc % 8 == 0, "mmg_attention_varlen_fwd: bad pointer or ldc");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.cu = cu_seqlens; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = lse;
-    a.S = S_max; a.S_pad = cdiv(S_max, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    const size_t shm = (size_t)2 * a.S_pad * 128 + a.S_pad * 4;
-    const dim3 grid(B * heads);
-    const int nt = a.S_pad / 16;
-#define ATT_FWD(NT)                                                                                   \
-    do {                                                                                              \
-        mmg_allow_lds(attn_fwd_kernel<NT, false>, shm);                                               \
-        hipLaunchKernelGGL((attn_fwd_kernel<NT, false>), grid, dim3(256), shm, stream, a);            \
-    } while (0)
-    if (nt <= 6) ATT_FWD(6);
-    else if (nt <= 8) ATT_FWD(8);
-    else if (nt <= 16) ATT_FWD(16);
-    else ATT_FWD(32);
-#undef ATT_FWD
+    AttArgs a;
+    if (att_args(a, "mmg_attention_varlen_fwd", 512, ATT_PACKED, qkv, ld, nullptr, cu_seqlens, ctx, ldc, lse, B, S_max, heads, Hd, scale)) return 1;
+    att_launch_fwd<false>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_varlen_fwd");
     return 0;
 }
@@ -466,16 +495,10 @@ MMG_API int mmg_attention_varlen_fwd(const void* qkv, int ld, const int* cu_seql
 MMG_API int mmg_attention_varlen_bwd(const void* qkv, int ld, const int* cu_seqlens, const void* ctx, int ldc, const float* lse,
                                      const void* dctx, int lddc, void* dqkv, int lddq, int B, int S_max, int heads, int Hd,
                                      float scale, hipStream_t stream) {
-    if (att_check("mmg_attention_varlen_bwd", B, S_max, heads, Hd, ld, 256)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && cu_seqlens && ldc >= Hd && lddc >= Hd && lddq >= 3 * Hd && ldc % 8 == 0 &&
-                      lddc % 8 == 0 && lddq % 8 == 0, "mmg_attention_varlen_bwd: bad pointer or leading dimension");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.cu = cu_seqlens; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = const_cast<float*>(lse);
-    a.S = S_max; a.S_pad = cdiv(S_max, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    a.dctx = (const bf16_t*)dctx; a.lddc = lddc; a.dqkv = (bf16_t*)dqkv; a.lddq = lddq;
-    const size_t shm = (size_t)4 * a.S_pad * 128 + 3 * a.S_pad * 4;
-    mmg_allow_lds(attn_bwd_kernel<false>, shm);
-    hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(B * heads), dim3(256), shm, stream, a);
+    AttArgs a;
+    const AttBwdOps bwd = {dctx, lddc, dqkv, lddq, nullptr};
+    if (att_args(a, "mmg_attention_varlen_bwd", 256, ATT_PACKED, qkv, ld, nullptr, cu_seqlens, ctx, ldc, lse, B, S_max, heads, Hd, scale, &bwd)) return 1;
+    att_launch_bwd<false>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_varlen_bwd");
     return 0;
 }
@@ -483,38 +506,13 @@ MMG_API int mmg_attention_varlen_bwd(const void* qkv, int ld, const int* cu_seql
 // Training-mode attention with dropout of the probabilities (dropout.h; HF BertSelfAttention.dropout, live in the reference's
 // training loop).  One entry point for both layouts: cu_seqlens != nullptr selects the packed layout (mask unused), otherwise the
 // padded one with its key mask.  `site` separates the layers' masks; the backward must be given the forward's (p, seed, site).
-static int att_drop_args(const char* who, float p, unsigned long long seed, unsigned site, DropArgs& d) {
-    MMG_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability %g must be in [0, 1)", who, (double)p);
-    d.key = mmg_drop_key(seed, site);
-    d.thresh = mmg_drop_threshold(p);
-    d.scale = 1.0f / (1.0f - p);
-    return 0;
-}
-
 MMG_API int mmg_attention_dropout_fwd(const void* qkv, int ld, const long long* mask, const int* cu_seqlens, void* ctx, int ldc,
                                       float* lse, int B, int S, int heads, int Hd, float scale, float p, unsigned long long seed,
                                       unsigned site, int first_sequence, hipStream_t stream) {
-    if (att_check("mmg_attention_dropout_fwd", B, S, heads, Hd, ld, 512)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && ldc >= Hd && ldc % 8 == 0, "mmg_attention_dropout_fwd: bad ctx");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.cu = cu_seqlens; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = lse;
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    if (att_drop_args("mmg_attention_dropout_fwd", p, seed, site, a.drop)) return 1;
-    MMG_CHECK_ARG(first_sequence >= 0, "mmg_attention_dropout_fwd: first_sequence %d", first_sequence);
-    a.bh0 = first_sequence * heads;
-    const size_t shm = (size_t)2 * a.S_pad * 128 + a.S_pad * 4;
-    const dim3 grid(B * heads);
-    const int nt = a.S_pad / 16;
-#define ATT_FWD(NT)                                                                                   \
-    do {                                                                                              \
-        mmg_allow_lds(attn_fwd_kernel<NT, true>, shm);                                                \
-        hipLaunchKernelGGL((attn_fwd_kernel<NT, true>), grid, dim3(256), shm, stream, a);             \
-    } while (0)
-    if (nt <= 6) ATT_FWD(6);
-    else if (nt <= 8) ATT_FWD(8);
-    else if (nt <= 16) ATT_FWD(16);
-    else ATT_FWD(32);
-#undef ATT_FWD
+    AttArgs a;
+    const AttDropout drop = {p, seed, site, first_sequence};
+    if (att_args(a, "mmg_attention_dropout_fwd", 512, 0, qkv, ld, mask, cu_seqlens, ctx, ldc, lse, B, S, heads, Hd, scale, nullptr, &drop)) return 1;
+    att_launch_fwd<true>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_dropout_fwd");
     return 0;
 }
@@ -523,20 +521,11 @@ MMG_API int mmg_attention_dropout_bwd(const void* qkv, int ld, const long long* 
                                       int ldc, const float* lse, const void* dctx, int lddc, void* dqkv, int lddq, int B, int S,
                                       int heads, int Hd, float scale, float p, unsigned long long seed, unsigned site,
                                       int first_sequence, hipStream_t stream) {
-    if (att_check("mmg_attention_dropout_bwd", B, S, heads, Hd, ld, 256)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && ldc >= Hd && lddc >= Hd && lddq >= 3 * Hd && ldc % 8 == 0 &&
-                      lddc % 8 == 0 && lddq % 8 == 0, "mmg_attention_dropout_bwd: bad pointer or leading dimension");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.cu = cu_seqlens; a.ctx = (bf16_t*)ctx; a.ldc = ldc;
-    a.lse = const_cast<float*>(lse);
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    a.dctx = (const bf16_t*)dctx; a.lddc = lddc; a.dqkv = (bf16_t*)dqkv; a.lddq = lddq;
-    if (att_drop_args("mmg_attention_dropout_bwd", p, seed, site, a.drop)) return 1;
-    MMG_CHECK_ARG(first_sequence >= 0, "mmg_attention_dropout_bwd: first_sequence %d", first_sequence);
-    a.bh0 = first_sequence * heads;
-    const size_t shm = (size_t)4 * a.S_pad * 128 + 3 * a.S_pad * 4;
-    mmg_allow_lds(attn_bwd_kernel<true>, shm);
-    hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(B * heads), dim3(256), shm, stream, a);
+    AttArgs a;
+    const AttBwdOps bwd = {dctx, lddc, dqkv, lddq, nullptr};
+    const AttDropout drop = {p, seed, site, first_sequence};
+    if (att_args(a, "mmg_attention_dropout_bwd", 256, 0, qkv, ld, mask, cu_seqlens, ctx, ldc, lse, B, S, heads, Hd, scale, &bwd, &drop)) return 1;
+    att_launch_bwd<true>(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_dropout_bwd");
     return 0;
 }
@@ -981,27 +970,74 @@ static int att_rb_env(const char* name, int max_rb) {
     return v == 3 ? 2 : v;                      // (3 only exists for dK/dV, where max_rb == 3 catches it above)
 }
 
+// Row blocks (of 16 rows) per wave: rbq for the forward and dQ kernels, rbk for dK/dV.  64 rows per wave (4 row blocks) once there are
+// enough blocks to fill the GPU twice over, else 32 / 16.  (The environment is read per call: the tests walk through 1 / 2 / 4.)
+static void att_rows_per_wave(const AttArgs& a, int& rbq, int& rbk) {
+    const int rbq_env = att_rb_env("MMG_ATT_RB", 4);
+    const int rbk_env = getenv("MMG_ATT_RB_DKV") ? att_rb_env("MMG_ATT_RB_DKV", 3) : (rbq_env > 2 ? 2 : rbq_env);
+    const long bhn = a.nbh;
+    rbq = rbq_env ? rbq_env : (bhn * cdiv(a.S, 256) >= 1024 ? 4 : bhn * cdiv(a.S, 128) >= 1024 ? 2 : 1);
+    // dK/dV holds two accumulator sets per row block: 3 blocks per wave is what fits 256 registers (measured -4 % vs 2)
+    rbk = rbk_env ? rbk_env : (bhn * cdiv(a.S, 192) >= 1024 ? 3 : bhn * cdiv(a.S, 128) >= 1024 ? 2 : 1);
+}
+
+// tiled forward: 64 RB query rows per workgroup, the MASK instantiation when there is a key mask
+static void att_launch_tiled_fwd(AttArgs a, hipStream_t stream) {
+    int rb, rbk;
+    att_rows_per_wave(a, rb, rbk);
+    a.nblk = cdiv(a.S, 64 * rb);
+    const dim3 grid((unsigned)((long)a.nbh * a.nblk));
+#define ATT_TILED_FWD(RBV)                                                                                   \
+    do {                                                                                                     \
+        if (a.mask) hipLaunchKernelGGL((attn_flash_fwd_kernel<RBV, true>), grid, dim3(256), 0, stream, a);   \
+        else hipLaunchKernelGGL((attn_flash_fwd_kernel<RBV, false>), grid, dim3(256), 0, stream, a);         \
+    } while (0)
+    if (rb == 4) ATT_TILED_FWD(4); else if (rb == 2) ATT_TILED_FWD(2); else ATT_TILED_FWD(1);
+#undef ATT_TILED_FWD
+}
+
+// tiled backward: delta = rowsum(dO * O) into the workspace, then dQ by query block, then dK/dV by key block.
+// DROP (S <= 512: 128-row workgroups): two row blocks per wave in both kernels - the only dropout instantiations there are (and
+// the only ones this template may name: a dispatch over RB under DROP would compile six more kernels).
+template <bool DROP>
+static void att_launch_tiled_bwd(AttArgs a, float* delta_ws, hipStream_t stream) {
+    const long rows = (long)a.nbh * a.S;
+    const int blocks = (int)((rows + 31) / 32 > 8192 ? 8192 : (rows + 31) / 32);          // 32 (row, head) pairs per workgroup
+    hipLaunchKernelGGL(attn_delta_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)a.ctx, a.ldc, a.dctx, a.lddc, delta_ws,
+                       a.nbh / a.heads, a.S, a.heads);
+    const float* dws = delta_ws;
+    if constexpr (DROP) {
+        a.nblk = cdiv(a.S, 64 * 2);
+        const dim3 grid((unsigned)((long)a.nbh * a.nblk));
+        if (a.mask) {
+            hipLaunchKernelGGL((attn_flash_dq_kernel<2, true, true>), grid, dim3(256), 0, stream, a, dws);
+            hipLaunchKernelGGL((attn_flash_dkv_kernel<2, true, true>), grid, dim3(256), 0, stream, a, dws);
+        } else {
+            hipLaunchKernelGGL((attn_flash_dq_kernel<2, false, true>), grid, dim3(256), 0, stream, a, dws);
+            hipLaunchKernelGGL((attn_flash_dkv_kernel<2, false, true>), grid, dim3(256), 0, stream, a, dws);
+        }
+    } else {
+#define ATT_TILED_BWD(KERNEL, RBV)                                                                             \
+    do {                                                                                                       \
+        a.nblk = cdiv(a.S, 64 * RBV);                                                                          \
+        const dim3 grid((unsigned)((long)a.nbh * a.nblk));                                                     \
+        if (a.mask) hipLaunchKernelGGL((KERNEL<RBV, true>), grid, dim3(256), 0, stream, a, dws);               \
+        else hipLaunchKernelGGL((KERNEL<RBV, false>), grid, dim3(256), 0, stream, a, dws);                     \
+    } while (0)
+        int rbq, rbk;
+        att_rows_per_wave(a, rbq, rbk);
+        if (rbq == 4) ATT_TILED_BWD(attn_flash_dq_kernel, 4); else if (rbq == 2) ATT_TILED_BWD(attn_flash_dq_kernel, 2); else ATT_TILED_BWD(attn_flash_dq_kernel, 1);
+        if (rbk == 3) ATT_TILED_BWD(attn_flash_dkv_kernel, 3); else if (rbk == 2) ATT_TILED_BWD(attn_flash_dkv_kernel, 2); else ATT_TILED_BWD(attn_flash_dkv_kernel, 1);
+#undef ATT_TILED_BWD
+    }
+}
+
 // Tiled (flash-style) attention for any S: same contract as mmg_attention_fwd.
 MMG_API int mmg_attention_long_fwd(const void* qkv, int ld, const long long* mask, void* ctx, int ldc, float* lse, int B, int S,
                                    int heads, int Hd, float scale, hipStream_t stream) {
-    if (att_check("mmg_attention_long_fwd", B, S, heads, Hd, ld, 1 << 20)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && ldc >= Hd && ldc % 8 == 0 && (long)B * heads <= 0x7fffffffL, "mmg_attention_long_fwd: bad ctx");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = lse;
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    // 64 rows per wave (4 row blocks) once there are enough query blocks to fill the GPU twice over, else 32 / 16
-    const int rb_env = att_rb_env("MMG_ATT_RB", 4);      // (read per call: the tests walk through 1 / 2 / 4)
-    const long bhn = (long)B * heads;
-    const int rb = rb_env ? rb_env : (bhn * cdiv(S, 256) >= 1024 ? 4 : bhn * cdiv(S, 128) >= 1024 ? 2 : 1);
-    a.nbh = (int)bhn; a.nblk = cdiv(S, 64 * rb);
-    const dim3 grid((unsigned)(bhn * a.nblk));
-#define ATT_FWD(RBV)                                                                                         \
-    do {                                                                                                     \
-        if (mask) hipLaunchKernelGGL((attn_flash_fwd_kernel<RBV, true>), grid, dim3(256), 0, stream, a);     \
-        else hipLaunchKernelGGL((attn_flash_fwd_kernel<RBV, false>), grid, dim3(256), 0, stream, a);         \
-    } while (0)
-    if (rb == 4) ATT_FWD(4); else if (rb == 2) ATT_FWD(2); else ATT_FWD(1);
-#undef ATT_FWD
+    AttArgs a;
+    if (att_args(a, "mmg_attention_long_fwd", 1 << 20, ATT_TILED, qkv, ld, mask, nullptr, ctx, ldc, lse, B, S, heads, Hd, scale)) return 1;
+    att_launch_tiled_fwd(a, stream);
     MMG_LAUNCH_CHECK("mmg_attention_long_fwd");
     return 0;
 }
@@ -1010,35 +1046,10 @@ MMG_API int mmg_attention_long_fwd(const void* qkv, int ld, const long long* mas
 MMG_API int mmg_attention_long_bwd(const void* qkv, int ld, const long long* mask, const void* ctx, int ldc, const float* lse,
                                    const void* dctx, int lddc, void* dqkv, int lddq, float* delta_ws, int B, int S, int heads,
                                    int Hd, float scale, hipStream_t stream) {
-    if (att_check("mmg_attention_long_bwd", B, S, heads, Hd, ld, 1 << 20)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta_ws && ldc >= Hd && lddc >= Hd && lddq >= 3 * Hd && ldc % 8 == 0 &&
-                      lddc % 8 == 0 && lddq % 8 == 0, "mmg_attention_long_bwd: bad pointer or leading dimension");
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = const_cast<float*>(lse);
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    a.dctx = (const bf16_t*)dctx; a.lddc = lddc; a.dqkv = (bf16_t*)dqkv; a.lddq = lddq;
-    long rows = (long)B * S * heads;
-    int blocks = (int)((rows + 31) / 32 > 8192 ? 8192 : (rows + 31) / 32);          // 32 (row, head) pairs per workgroup
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)ctx, ldc, (const bf16_t*)dctx, lddc,
-                       delta_ws, B, S, heads);
-    const int rbq_env = att_rb_env("MMG_ATT_RB", 4);
-    const int rbk_env = getenv("MMG_ATT_RB_DKV") ? att_rb_env("MMG_ATT_RB_DKV", 3) : (rbq_env > 2 ? 2 : rbq_env);
-    const long bhn = (long)B * heads;
-    const int rbq = rbq_env ? rbq_env : (bhn * cdiv(S, 256) >= 1024 ? 4 : bhn * cdiv(S, 128) >= 1024 ? 2 : 1);
-    // dK/dV holds two accumulator sets per row block: 3 blocks per wave is what fits 256 registers (measured -4 % vs 2)
-    const int rbk = rbk_env ? rbk_env : (bhn * cdiv(S, 192) >= 1024 ? 3 : bhn * cdiv(S, 128) >= 1024 ? 2 : 1);
-    const float* dws = (const float*)delta_ws;
-    a.nbh = (int)bhn;
-#define ATT_BWD(KERNEL, RBV)                                                                                   \
-    do {                                                                                                       \
-        a.nblk = cdiv(S, 64 * RBV);                                                                            \
-        const dim3 grid((unsigned)(bhn * a.nblk));                                                             \
-        if (mask) hipLaunchKernelGGL((KERNEL<RBV, true>), grid, dim3(256), 0, stream, a, dws);                 \
-        else hipLaunchKernelGGL((KERNEL<RBV, false>), grid, dim3(256), 0, stream, a, dws);                     \
-    } while (0)
-    if (rbq == 4) ATT_BWD(attn_flash_dq_kernel, 4); else if (rbq == 2) ATT_BWD(attn_flash_dq_kernel, 2); else ATT_BWD(attn_flash_dq_kernel, 1);
-    if (rbk == 3) ATT_BWD(attn_flash_dkv_kernel, 3); else if (rbk == 2) ATT_BWD(attn_flash_dkv_kernel, 2); else ATT_BWD(attn_flash_dkv_kernel, 1);
-#undef ATT_BWD
+    AttArgs a;
+    const AttBwdOps bwd = {dctx, lddc, dqkv, lddq, delta_ws};
+    if (att_args(a, "mmg_attention_long_bwd", 1 << 20, ATT_TILED, qkv, ld, mask, nullptr, ctx, ldc, lse, B, S, heads, Hd, scale, &bwd)) return 1;
+    att_launch_tiled_bwd<false>(a, delta_ws, stream);
     MMG_LAUNCH_CHECK("mmg_attention_long_bwd");
     return 0;
 }
@@ -1049,32 +1060,11 @@ MMG_API int mmg_attention_dropout_long_bwd(const void* qkv, int ld, const long l
                                            const void* dctx, int lddc, void* dqkv, int lddq, float* delta_ws, int B, int S, int heads,
                                            int Hd, float scale, float p, unsigned long long seed, unsigned site, int first_sequence,
                                            hipStream_t stream) {
-    if (att_check("mmg_attention_dropout_long_bwd", B, S, heads, Hd, ld, 512)) return 1;
-    MMG_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta_ws && ldc >= Hd && lddc >= Hd && lddq >= 3 * Hd && ldc % 8 == 0 &&
-                      lddc % 8 == 0 && lddq % 8 == 0, "mmg_attention_dropout_long_bwd: bad pointer or leading dimension");
-    MMG_CHECK_ARG(first_sequence >= 0, "mmg_attention_dropout_long_bwd: first_sequence %d", first_sequence);
-    AttArgs a = {};
-    a.qkv = (const bf16_t*)qkv; a.ld = ld; a.mask = mask; a.ctx = (bf16_t*)ctx; a.ldc = ldc; a.lse = const_cast<float*>(lse);
-    a.S = S; a.S_pad = cdiv(S, 32) * 32; a.heads = heads; a.Hd = Hd; a.scale = scale;
-    a.dctx = (const bf16_t*)dctx; a.lddc = lddc; a.dqkv = (bf16_t*)dqkv; a.lddq = lddq;
-    if (att_drop_args("mmg_attention_dropout_long_bwd", p, seed, site, a.drop)) return 1;
-    a.bh0 = first_sequence * heads;
-    long rows = (long)B * S * heads;
-    int blocks = (int)((rows + 31) / 32 > 8192 ? 8192 : (rows + 31) / 32);
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)ctx, ldc, (const bf16_t*)dctx, lddc,
-                       delta_ws, B, S, heads);
-    const long bhn = (long)B * heads;
-    const float* dws = (const float*)delta_ws;
-    a.nbh = (int)bhn;
-    a.nblk = cdiv(S, 64 * 2);                        // two row blocks per wave in both kernels (S <= 512: 128-row workgroups)
-    const dim3 grid((unsigned)(bhn * a.nblk));
-    if (mask) {
-        hipLaunchKernelGGL((attn_flash_dq_kernel<2, true, true>), grid, dim3(256), 0, stream, a, dws);
-        hipLaunchKernelGGL((attn_flash_dkv_kernel<2, true, true>), grid, dim3(256), 0, stream, a, dws);
-    } else {
-        hipLaunchKernelGGL((attn_flash_dq_kernel<2, false, true>), grid, dim3(256), 0, stream, a, dws);
-        hipLaunchKernelGGL((attn_flash_dkv_kernel<2, false, true>), grid, dim3(256), 0, stream, a, dws);
-    }
+    AttArgs a;
+    const AttBwdOps bwd = {dctx, lddc, dqkv, lddq, delta_ws};
+    const AttDropout drop = {p, seed, site, first_sequence};
+    if (att_args(a, "mmg_attention_dropout_long_bwd", 512, ATT_TILED, qkv, ld, mask, nullptr, ctx, ldc, lse, B, S, heads, Hd, scale, &bwd, &drop)) return 1;
+    att_launch_tiled_bwd<true>(a, delta_ws, stream);
     MMG_LAUNCH_CHECK("mmg_attention_dropout_long_bwd");
     return 0;
 }

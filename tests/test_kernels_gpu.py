@@ -218,6 +218,34 @@ def test_attention_fwd_long(dev):
     _close(ctx, _attn_ref(qkv, None, B, S, heads), 2e-2, 2e-2)
 
 
+@pytest.mark.parametrize("S_max,lens", [(77, (77, 19, 1)), (256, (256, 33))])
+def test_attention_varlen_fwd_bwd(dev, S_max, lens):
+    """Packed layout (mmg_attention_varlen_fwd / _bwd, the text tower's path with dropout off): a full-length sequence, one shorter
+    than a 32-row pad and a single token, each against the fp32 reference on its own rows; lse against the padded layout."""
+    from mmgclip import kernels as K
+    heads, B = 2, len(lens)
+    Hd = heads * 64
+    starts = [sum(lens[:b]) for b in range(B)]
+    cu = torch.tensor(starts + [sum(lens)], dtype=torch.int32, device=dev)
+    qkv = _r((sum(lens), 3 * Hd), dev, 51).to(BF)
+    dctx = _r((sum(lens), Hd), dev, 52).to(BF)
+    ctx, lse = K.attention_fwd(qkv, None, B, S_max, heads, cu=cu)
+    assert lse.shape == (B, heads, S_max)
+    dqkv = K.attention_bwd(qkv, None, ctx, lse, dctx, B, S_max, heads, cu=cu)
+    padded = torch.zeros(B, S_max, 3 * Hd, device=dev, dtype=BF)
+    for b, (r0, n) in enumerate(zip(starts, lens)):
+        padded[b, :n] = qkv[r0:r0 + n]
+    mask = (torch.arange(S_max)[None, :] < torch.tensor(lens)[:, None]).long().to(dev)
+    _, lse_padded = K.attention_fwd(padded.reshape(B * S_max, 3 * Hd), mask, B, S_max, heads)
+    for b, (r0, n) in enumerate(zip(starts, lens)):
+        qr = qkv[r0:r0 + n].float().requires_grad_(True)
+        ref = _attn_ref(qr, None, 1, n, heads)
+        _close(ctx[r0:r0 + n], ref, 2e-2, 2e-2)
+        ref.backward(dctx[r0:r0 + n].float())
+        _close(dqkv[r0:r0 + n], qr.grad, 5e-2, 5e-2)
+        _close(lse[b, :, :n], lse_padded[b, :, :n], 1e-4, 1e-4)
+
+
 def test_bert_embeddings_and_eos_pool(dev):
     from mmgclip import kernels as K
     B, S, H, V = 4, 77, 768, 1000
