@@ -40,6 +40,16 @@ int mmg_device_cu_count(void);
  * reference counterpart: the reference has no kernels of its own to name. */
 int mmg_set_kernel_notes(int on);
 const char* mmg_last_kernel(void);
+/* What a GEMM entry point WOULD launch for a shape, without launching: the plan its host layer makes (csrc/gemm_plan.h) as text -
+ * the exact mmg_last_kernel() spelling, then " grid=(x,y) block=T lds=B" (B = dynamic LDS bytes); the weight-gradient ops continue
+ * with " chunks=.. rows=.. xcd=.. swapped=.." (split of the reduction, rows per chunk, XCD grouping mode, operands exchanged) and the
+ * 8-bit ones with " split=..".  op: 0 mmg_gemm_nt_bf16, 1 mmg_gemm_nt_fp8, 2 / 3 mmg_gemm_nt_fp8_bwd with e5m2 / e4m3 A,
+ * 4 mmg_gemm_tn_bf16 (N = N1, K = N2), 5 / 6 mmg_gemm_tn_fp8 with e5m2 / e4m3 A (N = N1, K = N2); contiguous operands, no epilogue.
+ * cus: CU count the plan is made for, 0 = the current device's.  Honours the same environment knobs as the entry points.  A shape the
+ * entry point would reject gives "" and sets mmg_last_error() to that entry point's message.  The string belongs to the calling thread
+ * and is valid until its next call.  No reference counterpart (diagnostics; tests/test_gemm_plan_cpu.py pins kernel selection with it).
+ * Additive entry point: it came without an ABI version step (mmg_abi_version() stays 5). */
+const char* mmg_gemm_plan(int op, int M, int N, int K, int cus);
 
 /* ---- contrastive head (fp32, f32-input MFMA) ------------------------------------------------------------ */
 

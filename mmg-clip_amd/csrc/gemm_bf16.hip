@@ -21,7 +21,7 @@
 #include "common.h"
 #include <type_traits>
 #include "gemm_tn.h"
-#include <stdlib.h>
+#include "gemm_plan.h"
 
 #define GEMM_THREADS 256
 
@@ -30,7 +30,7 @@
 // Round 4: EPI_GELU_DAUX = GELU forward whose side output is GELU'(pre-activation) instead of the pre-activation, and
 // EPI_MUL_AUX = C = (A B^T) * aux_in - the data gradient of a layer whose forward kept GELU' (one multiply per element where EPI_DGELU_ONLY
 // evaluated a degree-7 polynomial: 19 000 of that tile's 53 600 cycles were this arithmetic, tools/nt_probe.py).
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_RELU = 3, EPI_DRELU = 4, EPI_DGELU_ONLY = 5, EPI_GELU_DAUX = 6, EPI_MUL_AUX = 7 };
+// (the EPI_* values: gemm_plan.h, beside the argument checks that admit them)
 
 struct GemmNT {
     const bf16_t* A; const bf16_t* B;
@@ -558,79 +558,47 @@ __global__ __launch_bounds__(WAVES_M * 128, BN > 128 ? 1 : ((NST == 3 && BK == 3
 #endif
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int NST, int F8 = 0>
-static void launch_nt(GemmNT& g, hipStream_t stream) {
-    g.tiles_m = cdiv(g.M, BM);
-    g.tiles_n = cdiv(g.N, BN);
-    const size_t stage = (size_t)NST * (BM * BK * 2 + BN * BK * 2);
-    const size_t cs = (size_t)64 * (BN + 4) * 4;
-    const size_t shm = stage > cs ? stage : cs;
-    mmg_allow_lds(gemm_nt_kernel<BM, BN, BK, WAVES_M, NST, F8>, shm);
-    MMG_NOTE_KERNEL("gemm_nt_kernel<%d, %d, %d, %d, %d, %d>", BM, BN, BK, WAVES_M, NST, F8);
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, BK, WAVES_M, NST, F8>), dim3(g.tiles_m * g.tiles_n), dim3(WAVES_M * 128), shm,
-                       stream, g);
+template <int BM, int BN, int BK, int WAVES_M, int NST, int F8>
+static void launch_nt(const GemmNT& g, const GemmPlan& p, hipStream_t stream) {
+    mmg_allow_lds(gemm_nt_kernel<BM, BN, BK, WAVES_M, NST, F8>, p.lds);
+    MMG_NOTE_KERNEL("%s", gemm_kernel_name(p.kernel));
+    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, BK, WAVES_M, NST, F8>), dim3(p.grid_x), dim3(p.block), p.lds, stream, g);
+}
+
+// The three NT doors: validate (gemm_plan.hip, before any HIP call), plan, launch what the plan names.
+// The fp8 kinds stage an 8-bit row of K bytes as a "bf16" row of K/2 elements: the kernel counts K, lda, ldb in 2-byte units.
+static int run_nt(int kind, const GemmNTArgs& a, hipStream_t stream) {
+    if (gemm_nt_check(kind, a)) return 1;
+    const GemmKnobs kn = gemm_knobs(kind == GEMM_NT_BF16 ? GEMM_LIVE_NT : 0);
+    const GemmPlan p = plan_nt(kind, a.M, a.N, a.K, kn);
+    const int eb = gemm_nt_elem_bytes(kind);
+    const int out_bytes = a.out_kind == GEMM_OUT_F32 ? 4 : a.out_kind == GEMM_OUT_BF16 ? 2 : 1;
+    GemmNT g;
+    g.A = (const bf16_t*)a.A; g.B = (const bf16_t*)a.B; g.M = a.M; g.N = a.N; g.K = a.K * eb / 2; g.lda = a.lda * eb / 2; g.ldb = a.ldb * eb / 2;
+    g.C = a.C; g.ldc = a.ldc; g.out_f32 = a.out_kind == GEMM_OUT_F32; g.bias = a.bias; g.colscale = a.colscale;
+    g.residual = (const bf16_t*)a.residual; g.ldr = a.ldr; g.aux_in = (const bf16_t*)a.aux_in; g.ldai = a.ldai;
+    g.aux_out = (bf16_t*)a.aux_out; g.ldao = a.ldao; g.epi = a.epi; g.alpha = a.alpha;
+    g.tiles_m = p.tiles1; g.tiles_n = p.tiles2;
+    g.nt_store = plan_nt_store(kind, a.M, a.N, out_bytes, kn);
+    g.out_fp8 = a.out_kind == GEMM_OUT_E4M3 ? 1 : a.out_kind == GEMM_OUT_E5M2 ? 2 : 0;
+    g.alpha_dev = a.alpha_dev; g.alpha_dev2 = a.alpha_dev2;
+    switch (p.kernel) {
+#define X(BM, BN, BK, WM, NST, F8) case GK_NT_##BM##_##BN##_##BK##_##WM##_##NST##_##F8: launch_nt<BM, BN, BK, WM, NST, F8>(g, p, stream); break;
+        GEMM_NT_KERNELS(X)
+#undef X
+        default: mmg_set_error("%s: no kernel for plan %d", gemm_nt_door(kind), p.kernel); return 1;
+    }
+    MMG_LAUNCH_CHECK(gemm_nt_door(kind));
+    return 0;
 }
 
 MMG_API int mmg_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                              const float* bias, const float* colscale, const void* residual, int ldr,
                              const void* aux_in, int ldai, void* aux_out, int ldao, int epi, int out_f32, float alpha,
                              hipStream_t stream) {
-    MMG_CHECK_ARG(A && B && C, "mmg_gemm_nt_bf16: null operand");
-    MMG_CHECK_ARG(M > 0 && N > 0 && K > 0, "mmg_gemm_nt_bf16: M=%d N=%d K=%d must be positive", M, N, K);
-    MMG_CHECK_ARG(K % 32 == 0, "mmg_gemm_nt_bf16: K=%d must be a multiple of 32", K);
-    MMG_CHECK_ARG(N % 8 == 0, "mmg_gemm_nt_bf16: N=%d must be a multiple of 8", N);
-    MMG_CHECK_ARG(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0,
-                  "mmg_gemm_nt_bf16: leading dimensions must cover the row and be multiples of 8 (lda=%d ldb=%d ldc=%d)",
-                  lda, ldb, ldc);
-    MMG_CHECK_ARG(epi >= EPI_NONE && epi <= EPI_MUL_AUX, "mmg_gemm_nt_bf16: unknown epilogue %d", epi);
-    MMG_CHECK_ARG(!(epi == EPI_DGELU || epi == EPI_DGELU_ONLY || epi == EPI_DRELU || epi == EPI_MUL_AUX) || (aux_in && ldai >= N && ldai % 8 == 0),
-                  "mmg_gemm_nt_bf16: activation-gradient epilogue needs aux_in");
-    MMG_CHECK_ARG(!residual || (ldr >= N && ldr % 8 == 0), "mmg_gemm_nt_bf16: bad ldr=%d", ldr);
-    MMG_CHECK_ARG(!aux_out || (ldao >= N && ldao % 8 == 0), "mmg_gemm_nt_bf16: bad ldao=%d", ldao);
-    GemmNT g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
-    g.C = C; g.ldc = ldc; g.out_f32 = out_f32; g.bias = bias; g.colscale = colscale;
-    g.residual = (const bf16_t*)residual; g.ldr = ldr; g.aux_in = (const bf16_t*)aux_in; g.ldai = ldai;
-    g.aux_out = (bf16_t*)aux_out; g.ldao = ldao; g.epi = epi; g.alpha = alpha; g.out_fp8 = 0; g.alpha_dev = nullptr; g.alpha_dev2 = nullptr;
-    static const int force_bk = getenv("MMG_GEMM_BK") ? atoi(getenv("MMG_GEMM_BK")) : 0;   // tuning knobs
-    static const int use_big = getenv("MMG_GEMM_V2") ? atoi(getenv("MMG_GEMM_V2")) : 1;
-    // outputs larger than the 256 MiB Infinity Cache cannot be re-read from cache anyway: stream them past L2
-    // (measured: -14...-20 % on the write-heavy GELU / residual epilogues); MMG_GEMM_NT_STORE=0/1 forces it off/on
-    static const int nt_mode = getenv("MMG_GEMM_NT_STORE") ? atoi(getenv("MMG_GEMM_NT_STORE")) : -1;
-    g.nt_store = nt_mode >= 0 ? nt_mode : ((size_t)M * N * (out_f32 ? 4 : 2) >= ((size_t)256 << 20));
-    const bool k64 = (K % 64 == 0) && force_bk != 32;
-    // N tile: 96 when it divides N and 128 does not (ConvNeXt widths 96/192), else 128
-    const bool n96 = (N % 128 != 0) && (N % 96 == 0);
-    // K < 384 (ConvNeXt stages 1-2, stem): HBM/latency bound -> 16 KiB stages, three of them, three workgroups per CU
-    static const int use_3wg = getenv("MMG_GEMM_3WG") ? atoi(getenv("MMG_GEMM_3WG")) : 1;
-    // (round 2, tools/nt_knobs.py, profiles/r02_nt_tile_rules.txt: the 4.2 M x 384 x 192 data gradient of the first downsample layer ran
-    // 30 % faster on the two-stage 128 x 128 x 64 tile than on the three-workgroup one, the N = 384 long-K shapes 2-4 % faster on it than
-    // on 256 x 128; BERT's shapes do not care)
-    static const int k3_max = getenv("MMG_GEMM_K3") ? atoi(getenv("MMG_GEMM_K3")) : 128;       // 3-WG config below this K
-    static const int kbig_min = getenv("MMG_GEMM_KBIG") ? atoi(getenv("MMG_GEMM_KBIG")) : 4096; // 256x128 config from this K
-    // 256x256 tile (8 waves, one workgroup per CU): 128 FLOP per operand byte pulled from L2, which is what bounds the
-    // 128-wide tiles (~10 TB/s of L2->LDS traffic); used from this K upwards when N is a multiple of 256 (0 = never)
-    static const int use_256 = getenv("MMG_GEMM_256") ? atoi(getenv("MMG_GEMM_256")) : 384;
-    // one workgroup per CU for the 256-row tiles: a grid that fills the last round of 256 CUs badly (BERT's ~10 k packed
-    // tokens x N = 768: 123 tiles = 48 % of one round) goes to the next smaller tile when that one fills better
-    static const int fill_rule = getenv("MMG_GEMM_FILL") ? atoi(getenv("MMG_GEMM_FILL")) : 1;
-    auto fill = [](long wgs) { return (double)wgs / (double)(cdiv(wgs, 256) * 256L); };
-    const double f256 = fill((long)cdiv(M, 256) * cdiv(N, 256)), f128 = fill((long)cdiv(M, 256) * cdiv(N, 128));
-    const bool fills = !fill_rule || f256 >= 0.8 * f128;
-    // (round 3, tools/nt_deep_ab.sh: the same tile on 32-column stages, three or four of them - more K tiles in flight at short K - was 2-3 %
-    // SLOWER on the K = 384 / 768 fat-epilogue shapes, 2883 / 2915 against 2827 us: the main loop is not waiting for its operands.  Removed.)
-    // round 4: N = 192 / 384 (ConvNeXt stage-3 d LN-out = dh W1: 1 M x 384 x 1536, 13.6 ms of a C2 step on 128 x 128 tiles at 0.33 of the MFMA peak)
-    // take a 256 x 192 tile - the 256 x 256 kernel's 8 waves with 64 x 96 wave tiles (0.42 fragment reads per MFMA against 0.5)
-    const int use_192 = getenv("MMG_GEMM_192") ? atoi(getenv("MMG_GEMM_192")) : 384;      // (read per call: same-process A/B, tools/nt_192_ab.py)
-    const double f192 = fill((long)cdiv(M, 256) * cdiv(N, 192));
-    if (use_256 && k64 && N % 256 == 0 && M >= 4096 && K >= use_256 && fills) launch_nt<256, 256, 64, 4, 2>(g, stream);
-    else if (use_192 && k64 && N % 192 == 0 && M >= 4096 && K >= use_192 && (!fill_rule || f192 >= 0.8 * f128)) launch_nt<256, 192, 64, 4, 2>(g, stream);
-    else if (use_3wg && !n96 && K % 32 == 0 && K < k3_max) launch_nt<128, 128, 32, 2, 3>(g, stream);
-    else if (use_big && k64 && !n96 && M >= 4096 && K >= kbig_min) launch_nt<256, 128, 64, 4, 3>(g, stream);
-    else if (n96) { if (k64) launch_nt<128, 96, 64, 2, 2>(g, stream); else launch_nt<128, 96, 32, 2, 2>(g, stream); }
-    else          { if (k64) launch_nt<128, 128, 64, 2, 2>(g, stream); else launch_nt<128, 128, 32, 2, 2>(g, stream); }
-    MMG_LAUNCH_CHECK("mmg_gemm_nt_bf16");
-    return 0;
+    const GemmNTArgs a = {A, lda, B, ldb, C, ldc, M, N, K, bias, colscale, residual, ldr, aux_in, ldai, aux_out, ldao,
+                          epi, out_f32 ? GEMM_OUT_F32 : GEMM_OUT_BF16, alpha, nullptr, nullptr};
+    return run_nt(GEMM_NT_BF16, a, stream);
 }
 
 // e4m3 x e4m3 -> fp32 accumulate on the double-rate K = 128 MFMA; same tiles, staging and epilogues as the bf16 kernel
@@ -638,29 +606,9 @@ MMG_API int mmg_gemm_nt_bf16(const void* A, int lda, const void* B, int ldb, voi
 MMG_API int mmg_gemm_nt_fp8(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                             const float* bias, const float* colscale, const void* residual, int ldr, void* aux_out,
                             int ldao, int epi, int out_kind, float alpha, const float* alpha_dev, hipStream_t stream) {
-    MMG_CHECK_ARG(A && B && C, "mmg_gemm_nt_fp8: null operand");
-    MMG_CHECK_ARG(M > 0 && N > 0 && K > 0, "mmg_gemm_nt_fp8: M=%d N=%d K=%d must be positive", M, N, K);
-    MMG_CHECK_ARG(K % 128 == 0, "mmg_gemm_nt_fp8: K=%d must be a multiple of 128 (one MFMA k-step)", K);
-    MMG_CHECK_ARG(N % 8 == 0, "mmg_gemm_nt_fp8: N=%d must be a multiple of 8", N);
-    MMG_CHECK_ARG(out_kind >= 0 && out_kind <= 2, "mmg_gemm_nt_fp8: out_kind=%d (0 bf16, 1 fp32, 2 e4m3)", out_kind);
-    MMG_CHECK_ARG(lda >= K && ldb >= K && ldc >= N && lda % 16 == 0 && ldb % 16 == 0 && ldc % 8 == 0,
-                  "mmg_gemm_nt_fp8: leading dimensions must cover the row; lda/ldb multiples of 16 bytes, ldc of 8 "
-                  "(lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
-    MMG_CHECK_ARG(epi == EPI_NONE || epi == EPI_GELU || epi == EPI_RELU || epi == EPI_GELU_DAUX, "mmg_gemm_nt_fp8: epilogue %d not available", epi);
-    MMG_CHECK_ARG(!residual || (ldr >= N && ldr % 8 == 0), "mmg_gemm_nt_fp8: bad ldr=%d", ldr);
-    MMG_CHECK_ARG(!aux_out || (ldao >= N && ldao % 8 == 0), "mmg_gemm_nt_fp8: bad ldao=%d", ldao);
-    GemmNT g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2;
-    g.C = C; g.ldc = ldc; g.out_f32 = out_kind == 1; g.out_fp8 = out_kind == 2; g.bias = bias; g.colscale = colscale;
-    g.residual = (const bf16_t*)residual; g.ldr = ldr; g.aux_in = nullptr; g.ldai = 0;
-    g.aux_out = (bf16_t*)aux_out; g.ldao = ldao; g.epi = epi; g.alpha = alpha; g.alpha_dev = alpha_dev; g.alpha_dev2 = nullptr;
-    g.nt_store = (size_t)M * N * (out_kind == 1 ? 4 : out_kind == 2 ? 1 : 2) >= ((size_t)256 << 20);
-    static const int tile = getenv("MMG_FP8_TILE") ? atoi(getenv("MMG_FP8_TILE")) : 0;   // tuning: 1 = 256x128, 2 = 128x128
-    if (tile == 0 && N % 256 == 0 && M >= 4096) launch_nt<256, 256, 64, 4, 2, 1>(g, stream);
-    else if (tile != 2 && M >= 4096) launch_nt<256, 128, 64, 4, 3, 1>(g, stream);
-    else launch_nt<128, 128, 64, 2, 2, 1>(g, stream);
-    MMG_LAUNCH_CHECK("mmg_gemm_nt_fp8");
-    return 0;
+    const GemmNTArgs a = {A, lda, B, ldb, C, ldc, M, N, K, bias, colscale, residual, ldr, nullptr, 0, aux_out, ldao,
+                          epi, out_kind, alpha, alpha_dev, nullptr};
+    return run_nt(GEMM_NT_FP8, a, stream);
 }
 
 // Data-gradient GEMMs of the fp8 backward (round 4): A = a gradient in OCP e5m2 (a_e5m2 != 0) or e4m3 bytes, B = e4m3 weights, fp32 accumulate on the
@@ -669,28 +617,9 @@ MMG_API int mmg_gemm_nt_fp8(const void* A, int lda, const void* B, int ldb, void
 MMG_API int mmg_gemm_nt_fp8_bwd(const void* A, int lda, int a_e5m2, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                                 const void* aux_in, int ldai, int epi, int out_kind, float alpha, const float* alpha_dev,
                                 const float* alpha_dev2, hipStream_t stream) {
-    MMG_CHECK_ARG(A && B && C, "mmg_gemm_nt_fp8_bwd: null operand");
-    MMG_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 128 == 0 && N % 8 == 0, "mmg_gemm_nt_fp8_bwd: M=%d N=%d K=%d (K a multiple of 128, N of 8)", M, N, K);
-    MMG_CHECK_ARG(out_kind == 0 || out_kind == 1 || out_kind == 3, "mmg_gemm_nt_fp8_bwd: out_kind=%d (0 bf16, 1 fp32, 3 e5m2)", out_kind);
-    MMG_CHECK_ARG(lda >= K && ldb >= K && ldc >= N && lda % 16 == 0 && ldb % 16 == 0 && ldc % 8 == 0,
-                  "mmg_gemm_nt_fp8_bwd: leading dimensions must cover the row; lda/ldb multiples of 16 bytes, ldc of 8 (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
-    MMG_CHECK_ARG(epi == EPI_NONE || epi == EPI_DGELU_ONLY || epi == EPI_MUL_AUX, "mmg_gemm_nt_fp8_bwd: epilogue %d not available", epi);
-    MMG_CHECK_ARG(epi == EPI_NONE || (aux_in && ldai >= N && ldai % 8 == 0), "mmg_gemm_nt_fp8_bwd: the activation-gradient epilogues need aux_in");
-    GemmNT g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2;
-    g.C = C; g.ldc = ldc; g.out_f32 = out_kind == 1; g.out_fp8 = out_kind == 3 ? 2 : 0; g.bias = nullptr; g.colscale = nullptr;
-    g.residual = nullptr; g.ldr = 0; g.aux_in = (const bf16_t*)aux_in; g.ldai = ldai; g.aux_out = nullptr; g.ldao = 0;
-    g.epi = epi; g.alpha = alpha; g.alpha_dev = alpha_dev; g.alpha_dev2 = alpha_dev2;
-    g.nt_store = (size_t)M * N * (out_kind == 1 ? 4 : out_kind == 3 ? 1 : 2) >= ((size_t)256 << 20);
-    if (a_e5m2) {
-        if (N % 256 == 0 && M >= 4096) launch_nt<256, 256, 64, 4, 2, 2>(g, stream);
-        else launch_nt<128, 128, 64, 2, 2, 2>(g, stream);
-    } else {
-        if (N % 256 == 0 && M >= 4096) launch_nt<256, 256, 64, 4, 2, 1>(g, stream);
-        else launch_nt<128, 128, 64, 2, 2, 1>(g, stream);
-    }
-    MMG_LAUNCH_CHECK("mmg_gemm_nt_fp8_bwd");
-    return 0;
+    const GemmNTArgs a = {A, lda, B, ldb, C, ldc, M, N, K, nullptr, nullptr, nullptr, 0, aux_in, ldai, nullptr, 0,
+                          epi, out_kind, alpha, alpha_dev, alpha_dev2};
+    return run_nt(a_e5m2 ? GEMM_NT_FP8_BWD_E5M2 : GEMM_NT_FP8_BWD_E4M3, a, stream);
 }
 
 // =============================================================================================
@@ -882,61 +811,32 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_tn_kernel(const GemmTN g
 }
 
 template <int K1, int K2, int BK>
-static void launch_tn(GemmTN& g, hipStream_t stream) {
-    static const int target_wgs = getenv("MMG_TN_WGS") ? atoi(getenv("MMG_TN_WGS")) : 512;
-    static const int xcd = getenv("MMG_TN_XCD") ? atoi(getenv("MMG_TN_XCD")) : 1;
-    g.tiles1 = cdiv(g.N1, K1 * TN_T);
-    g.tiles2 = cdiv(g.N2, K2 * TN_T);
-    const int tiles = g.tiles1 * g.tiles2;
-    int chunks = target_wgs / tiles;
-    if (chunks < 1) chunks = 1;
-    const int max_chunks = cdiv(g.M, 64);
-    if (chunks > max_chunks) chunks = max_chunks;
-    g.rows_per_chunk = cdiv(cdiv(g.M, chunks), 64) * 64;
-    chunks = cdiv(g.M, g.rows_per_chunk);
-    g.chunks = chunks;
-    g.xcd_order = xcd ? (g.N2 >= g.N1 ? 1 : 2) : 0;
-    if (g.xcd_order) {       // whole groups per XCD: fall back when that would overfill an XCD's share of the workgroup budget
-        const int G = g.xcd_order == 1 ? g.tiles1 : g.tiles2, ngroups = (tiles / G) * chunks;
-        if (((ngroups + 7) / 8) * G * 8 > target_wgs && tiles * chunks <= target_wgs) g.xcd_order = 0;
-    }
-    const size_t stage = 2 * (size_t)(K1 + K2) * (BK * TN_T * 2);
-    const size_t cs = (size_t)64 * (K2 * TN_T + 4) * 4;
-    const size_t shm = stage > cs ? stage : cs;
-    mmg_allow_lds(gemm_tn_kernel<K1, K2, BK>, shm);
-    MMG_NOTE_KERNEL("gemm_tn_kernel<%d, %d, %d>", K1, K2, BK);
-    if (g.xcd_order) {
-        const int G = g.xcd_order == 1 ? g.tiles1 : g.tiles2, ngroups = (tiles / G) * chunks;
-        hipLaunchKernelGGL((gemm_tn_kernel<K1, K2, BK>), dim3(8 * ((ngroups + 7) / 8) * G), dim3(GEMM_THREADS), shm, stream, g);
-    } else {
-        hipLaunchKernelGGL((gemm_tn_kernel<K1, K2, BK>), dim3(tiles, chunks), dim3(GEMM_THREADS), shm, stream, g);
-    }
+static void launch_tn(const GemmTN& g, const GemmPlan& p, hipStream_t stream) {
+    mmg_allow_lds(gemm_tn_kernel<K1, K2, BK>, p.lds);
+    MMG_NOTE_KERNEL("%s", gemm_kernel_name(p.kernel));
+    hipLaunchKernelGGL((gemm_tn_kernel<K1, K2, BK>), dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, stream, g);
 }
 
 MMG_API int mmg_gemm_tn_bf16(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N1, int N2,
                              float alpha, float* colsum_a, hipStream_t stream) {
-    MMG_CHECK_ARG(A && B && C, "mmg_gemm_tn_bf16: null operand");
-    MMG_CHECK_ARG(M > 0 && N1 >= 8 && N2 >= 8, "mmg_gemm_tn_bf16: M=%d N1=%d N2=%d", M, N1, N2);
-    MMG_CHECK_ARG(N1 % 8 == 0 && N2 % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= N1 && ldb >= N2 && ldc >= N2,
-                  "mmg_gemm_tn_bf16: N1=%d N2=%d lda=%d ldb=%d ldc=%d must be multiples of 8 and consistent", N1, N2,
-                  lda, ldb, ldc);
+    const GemmTNArgs a = {A, lda, B, ldb, C, ldc, M, N1, N2};
+    if (gemm_tn_check(0, a)) return 1;
+    const GemmPlan p = plan_tn(M, N1, N2, gemm_knobs(GEMM_LIVE_TN));
     GemmTN g;
     g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.M = M; g.N1 = N1; g.N2 = N2; g.lda = lda; g.ldb = ldb;
     g.C = C; g.ldc = ldc; g.alpha = alpha; g.colsum_a = colsum_a;
-    // 256-wide tiles on the wider side when it is a multiple of 256 (measured: -6...-19 % on the ConvNeXt shapes, slower on
-    // the short BERT reductions where the tile count is what fills the GPU); MMG_TN_WIDE=0 disables
-    static const int wide = getenv("MMG_TN_WIDE") ? atoi(getenv("MMG_TN_WIDE")) : 1;
-    // long reductions onto few output columns (ConvNeXt weight gradients): the 8-wave wide-tile kernel (gemm_tn_wide.hip) streams
-    // both operands once per 192x384-class tile; MMG_TN_WIDE8=0 keeps the kernels of this file
-    const int wide8 = getenv("MMG_TN_WIDE8") ? atoi(getenv("MMG_TN_WIDE8")) : 1;
-    if (wide8 && mmg_tn_wide_launch(g, stream)) {
-        MMG_LAUNCH_CHECK("mmg_gemm_tn_bf16");
-        return 0;
+    g.tiles1 = p.tiles1; g.tiles2 = p.tiles2; g.rows_per_chunk = p.rows_per_chunk; g.chunks = p.chunks; g.xcd_order = p.xcd;
+    g.swapped = p.swapped;
+    if (p.swapped) {         // (gemm_tn_wide_kernel only) the wide side becomes N2
+        g.A = (const bf16_t*)B; g.B = (const bf16_t*)A; g.N1 = N2; g.N2 = N1; g.lda = ldb; g.ldb = lda;
     }
-    const bool long_m = M >= 32768;
-    if (wide && long_m && N2 >= N1 && N2 % 256 == 0) launch_tn<1, 2, 32>(g, stream);
-    else if (wide && long_m && N1 > N2 && N1 % 256 == 0) launch_tn<2, 1, 32>(g, stream);
-    else launch_tn<1, 1, 64>(g, stream);
+    switch (p.kernel) {
+#define X(K1, K2, BK) case GK_TN_##K1##_##K2##_##BK: launch_tn<K1, K2, BK>(g, p, stream); break;
+        GEMM_TN_KERNELS(X)
+#undef X
+        default:
+            if (!mmg_tn_wide_launch(g, p, stream)) { mmg_set_error("mmg_gemm_tn_bf16: no kernel for plan %d", p.kernel); return 1; }
+    }
     MMG_LAUNCH_CHECK("mmg_gemm_tn_bf16");
     return 0;
 }

@@ -16,5 +16,6 @@ struct GemmTN {
     int swapped;
 };
 
-// Launches the wide-tile kernel when the shape suits it; returns false (nothing launched) otherwise.
-bool mmg_tn_wide_launch(GemmTN& g, hipStream_t stream);
+// Launches the gemm_tn_wide_kernel instantiation the plan names; returns false (nothing launched) when it names none.
+struct GemmPlan;
+bool mmg_tn_wide_launch(const GemmTN& g, const GemmPlan& p, hipStream_t stream);

@@ -13,7 +13,7 @@
 // address and on the read) with ((m >> 1) & 3) | (((m >> 5) & 1) << 2): the 8 rows of a transposed read then sit in 8 different (slot, bank-row half)
 // places and the two 16-lane groups of a half wave (k ranges 32 apart) in disjoint slots - conflict-free by the bank model of the microarchitecture guide.
 #include "common.h"
-#include <stdlib.h>
+#include "gemm_plan.h"
 
 #define T8_T 128          // output tile edge
 #define T8_BK 128         // reduction rows per stage = one k-step of the K = 128 MFMA
@@ -339,55 +339,37 @@ __global__ __launch_bounds__(W8_THREADS, 2) void gemm_tn8_wide_kernel(const Gemm
     }
 }
 
+template <int AF>
+static void launch_t8(const GemmTN8& g, const GemmPlan& p, hipStream_t stream) {
+    mmg_allow_lds(gemm_tn8_kernel<AF>, p.lds);
+    MMG_NOTE_KERNEL("%s", gemm_kernel_name(p.kernel));
+    hipLaunchKernelGGL(gemm_tn8_kernel<AF>, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, stream, g);
+}
+template <int AF, bool CS>
+static void launch_w8(const GemmTN8& g, const GemmPlan& p, hipStream_t stream) {
+    mmg_allow_lds(gemm_tn8_wide_kernel<AF, CS>, p.lds);
+    MMG_NOTE_KERNEL("%s", gemm_kernel_name(p.kernel));
+    hipLaunchKernelGGL((gemm_tn8_wide_kernel<AF, CS>), dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, stream, g);
+}
+
 MMG_API int mmg_gemm_tn_fp8(const void* A, int lda, int a_e5m2, const void* B, int ldb, float* C, int ldc, int M, int N1, int N2,
                             float alpha, const float* alpha_dev, float* colsum_a, hipStream_t stream) {
-    MMG_CHECK_ARG(A && B && C, "mmg_gemm_tn_fp8: null operand");
-    MMG_CHECK_ARG(M > 0 && N1 >= 16 && N2 >= 16, "mmg_gemm_tn_fp8: M=%d N1=%d N2=%d", M, N1, N2);
-    MMG_CHECK_ARG(N1 % 16 == 0 && N2 % 16 == 0 && lda % 16 == 0 && ldb % 16 == 0 && lda >= N1 && ldb >= N2 && ldc >= N2,
-                  "mmg_gemm_tn_fp8: N1=%d N2=%d lda=%d ldb=%d ldc=%d must be multiples of 16 (bytes) and consistent", N1, N2, lda, ldb, ldc);
+    const GemmTNArgs a = {A, lda, B, ldb, C, ldc, M, N1, N2};
+    if (gemm_tn_check(1, a)) return 1;
+    const GemmPlan p = plan_tn8(a_e5m2, M, N1, N2, mmg_cu_count_cached(), gemm_knobs(GEMM_LIVE_TN8));
     GemmTN8 g;
     g.A = (const unsigned char*)A; g.B = (const unsigned char*)B; g.M = M; g.N1 = N1; g.N2 = N2; g.lda = lda; g.ldb = ldb;
     g.C = C; g.ldc = ldc; g.colsum_a = colsum_a; g.alpha = alpha; g.alpha_dev = alpha_dev;
-    // 256 x 256 tiles (one 8-wave workgroup per CU) where both widths fill them and the reduction is long; MMG_TN8_WIDE=0 / 1 forces
-    const char* ew = getenv("MMG_TN8_WIDE");
-    const bool wide = ew ? atoi(ew) != 0 : (N1 >= 256 && N2 >= 256 && M >= 8192);
-    const char* ex = getenv("MMG_TN8_XCD");
-    g.xcd_map = wide || !(ex && atoi(ex) == 0);
-    const int T = wide ? W8_T : T8_T;
-    g.tiles1 = cdiv(N1, T); g.tiles2 = cdiv(N2, T);
-    const int tiles = g.tiles1 * g.tiles2;
-    static const int target_wgs = getenv("MMG_TN8_WGS") ? atoi(getenv("MMG_TN8_WGS")) : 1024;      // two workgroups per CU, two rounds
-    int chunks = (wide ? mmg_cu_count_cached() : target_wgs) / tiles;
-    if (chunks < 1) chunks = 1;
-    const int max_chunks = cdiv(M, T8_BK);
-    if (chunks > max_chunks) chunks = max_chunks;
-    g.rows_per_chunk = cdiv(cdiv(M, chunks), T8_BK) * T8_BK;
-    g.chunks = cdiv(M, g.rows_per_chunk);
-    int S = 1;                                                 // (see t8_xcd_map)
-    while (S < 8 && ((g.chunks * S) % 8 != 0) && tiles % (2 * S) == 0) S *= 2;
-    g.xcd_split = S;
-    const int units8 = cdiv(g.chunks * S, 8) * 8;              // units are dealt in groups of 8 (workgroups past the last chunk return at once)
-    const dim3 grid = g.xcd_map ? dim3((tiles / S) * units8) : dim3(tiles, g.chunks);
-    if (wide) {
-        const size_t shm = 2 * (size_t)(2 * W8_SUB);           // (the fp32 flush slab, 64 x 260 x 4, fits inside)
-        MMG_NOTE_KERNEL("gemm_tn8_wide_kernel<%d>", a_e5m2 ? 1 : 0);
-#define W8_LAUNCH(AF_, CS_) do { mmg_allow_lds(gemm_tn8_wide_kernel<AF_, CS_>, shm); \
-                                 hipLaunchKernelGGL((gemm_tn8_wide_kernel<AF_, CS_>), grid, dim3(W8_THREADS), shm, stream, g); } while (0)
-        if (a_e5m2) { if (colsum_a) W8_LAUNCH(1, true); else W8_LAUNCH(1, false); }
-        else { if (colsum_a) W8_LAUNCH(0, true); else W8_LAUNCH(0, false); }
-#undef W8_LAUNCH
-        MMG_LAUNCH_CHECK("mmg_gemm_tn_fp8");
-        return 0;
-    }
-    const size_t stage = 2 * (size_t)(2 * T8_SUB), cs = (size_t)64 * (T8_T + 4) * 4;
-    const size_t shm = stage > cs ? stage : cs;
-    MMG_NOTE_KERNEL("gemm_tn8_kernel<%d>", a_e5m2 ? 1 : 0);
-    if (a_e5m2) {
-        mmg_allow_lds(gemm_tn8_kernel<1>, shm);
-        hipLaunchKernelGGL(gemm_tn8_kernel<1>, grid, dim3(T8_THREADS), shm, stream, g);
-    } else {
-        mmg_allow_lds(gemm_tn8_kernel<0>, shm);
-        hipLaunchKernelGGL(gemm_tn8_kernel<0>, grid, dim3(T8_THREADS), shm, stream, g);
+    g.tiles1 = p.tiles1; g.tiles2 = p.tiles2; g.rows_per_chunk = p.rows_per_chunk; g.chunks = p.chunks;
+    g.xcd_split = p.xcd_split; g.xcd_map = p.xcd;
+    switch (p.kernel) {
+#define X(AF) case GK_T8_##AF: launch_t8<AF>(g, p, stream); break;
+        GEMM_T8_KERNELS(X)
+#undef X
+#define X(AF) case GK_W8_##AF: if (colsum_a) launch_w8<AF, true>(g, p, stream); else launch_w8<AF, false>(g, p, stream); break;
+        GEMM_W8_KERNELS(X)
+#undef X
+        default: mmg_set_error("mmg_gemm_tn_fp8: no kernel for plan %d", p.kernel); return 1;
     }
     MMG_LAUNCH_CHECK("mmg_gemm_tn_fp8");
     return 0;

@@ -5,7 +5,7 @@
 // module tree of notebooks/clf_convnext_tiny_experimental.ipynb cell 3).  On the ConvNeXt shapes the reduction runs over
 // M = 0.26...16.8 million pixel rows onto at most 768 x 3072 outputs, so the kernel is a STREAM of the two operands:
 //
-//   * one 8-wave workgroup per CU owns a whole 192 x 384 (or 384 x 192 / 96 x 384 / 384 x 96) fp32 accumulator tile - 144
+//   * one 8-wave workgroup per CU owns a whole 192 x 384 (or 96 x 384 / 256 x 256 / 128 x 256) fp32 accumulator tile - 144
 //     registers per lane - for one contiguous chunk of rows, so every operand byte is staged 1/(tiles across) times instead of
 //     once per 128-wide tile (gemm_tn_kernel: 2.4...3.6x the algorithmic bytes through L2, 1.9x through HBM);
 //   * rows arrive by LDS-DMA (16-byte global_load_lds) into a ring of four 32-row stages, three of them in flight: counted
@@ -17,7 +17,7 @@
 //   * all tiles of a row chunk run on one XCD (blockIdx % 8), so re-reads of a chunk by the other tiles hit that XCD's L2;
 //   * accumulators leave through LDS as 256-byte contiguous fp32 atomic rows (the full-rate atomic shape), once per workgroup.
 #include "gemm_tn.h"
-#include <stdlib.h>
+#include "gemm_plan.h"
 #include <utility>
 
 #define TW_THREADS 512
@@ -27,9 +27,7 @@
 
 template <int T1, int T2> struct TwCfg;
 template <> struct TwCfg<192, 384> { static constexpr int W1 = 2, W2 = 4, FM = 6, FN = 6; };
-template <> struct TwCfg<384, 192> { static constexpr int W1 = 4, W2 = 2, FM = 6, FN = 6; };
 template <> struct TwCfg<96, 384>  { static constexpr int W1 = 1, W2 = 8, FM = 6, FN = 3; };
-template <> struct TwCfg<384, 96>  { static constexpr int W1 = 8, W2 = 1, FM = 3, FN = 6; };
 // ConvNeXt-B widths (128 / 256 / 512 / 1024): 256-wide tiles, 64 / 128 accumulator registers per lane
 template <> struct TwCfg<128, 256> { static constexpr int W1 = 2, W2 = 4, FM = 4, FN = 4; };
 template <> struct TwCfg<256, 256> { static constexpr int W1 = 2, W2 = 4, FM = 8, FN = 4; };
@@ -320,68 +318,19 @@ __global__ __launch_bounds__(TW_THREADS, 2) void gemm_tn_wide_kernel(const GemmT
     }
 }
 
-template <int T1, int T2>
-static void launch_tw(GemmTN& g, hipStream_t stream) {
-    using Cfg = TwCfg<T1, T2>;
-    g.tiles1 = cdiv(g.N1, T1);
-    g.tiles2 = cdiv(g.N2, T2);
-    const int ntile = g.tiles1 * g.tiles2;
-    // one workgroup per CU (149 KiB of LDS): 32 per XCD = the tiles of `cpx` row chunks
-    int cpx = 32 / ntile;
-    if (cpx < 1) cpx = 1;
-    int chunks = 8 * cpx;
-    g.rows_per_chunk = cdiv(cdiv(g.M, chunks), TW_BK) * TW_BK;
-    g.chunks = chunks;
-    constexpr int NIA = (T1 + 63) / 64, NIB = (T2 + 63) / 64;
-    const size_t ring = (size_t)TW_NS * (NIA + NIB) * TW_IMG;
-    const size_t cs = (size_t)Cfg::FM * 16 * (T2 + 4) * 4;
-    const size_t shm = ring > cs ? ring : cs;
-    mmg_allow_lds(gemm_tn_wide_kernel<T1, T2>, shm);
-    MMG_NOTE_KERNEL("gemm_tn_wide_kernel<%d, %d>", T1, T2);
-    hipLaunchKernelGGL((gemm_tn_wide_kernel<T1, T2>), dim3(8 * cpx * ntile), dim3(TW_THREADS), shm, stream, g);
+template <int T1, int T2, int FM>
+static void launch_tw(const GemmTN& g, const GemmPlan& p, hipStream_t stream) {
+    static_assert(TwCfg<T1, T2>::FM == FM, "gemm_plan.h sizes the flush slab with this FM");
+    mmg_allow_lds(gemm_tn_wide_kernel<T1, T2>, p.lds);
+    MMG_NOTE_KERNEL("%s", gemm_kernel_name(p.kernel));
+    hipLaunchKernelGGL((gemm_tn_wide_kernel<T1, T2>), dim3(p.grid_x), dim3(p.block), p.lds, stream, g);
 }
 
-bool mmg_tn_wide_launch(GemmTN& g, hipStream_t stream) {
-    static const int min_m = getenv("MMG_TN_WIDE8_MIN_M") ? atoi(getenv("MMG_TN_WIDE8_MIN_M")) : 65536;
-    // every workgroup flushes a whole tile with fp32 atomics (75 MB per launch at 256 workgroups of 192 x 384 = ~60 us): only
-    // reductions long enough to amortise that take this kernel
-    if (g.M < min_m || g.N1 < 96 || g.N2 < 96) return false;
-    const bool wide2 = g.N2 >= g.N1;                 // orientation: the wider side gets the wide tile edge (the 4 wave columns)
-    const int narrow = wide2 ? g.N1 : g.N2, wideN = wide2 ? g.N2 : g.N1;
-    // tile = (narrow edge, wide edge) with the least padding: 96 / 192 x 384 (ConvNeXt-T widths), 128 / 256 x 256 (ConvNeXt-B widths)
-    // (largest tile first: on equal padding the bigger accumulator tile wins - 384 x 1536 runs on 192 x 384 tiles, not 96 x 384)
-    static const int cfgs[4][2] = {{192, 384}, {256, 256}, {96, 384}, {128, 256}};
-    int best = -1;
-    double best_waste = 1e9;
-    for (int i = 0; i < 4; ++i) {
-        const double w = (double)(cdiv(narrow, cfgs[i][0]) * cfgs[i][0]) * (cdiv(wideN, cfgs[i][1]) * cfgs[i][1]) / ((double)narrow * wideN);
-        if (w < best_waste - 1e-9) { best_waste = w; best = i; }
+bool mmg_tn_wide_launch(const GemmTN& g, const GemmPlan& p, hipStream_t stream) {
+    switch (p.kernel) {
+#define X(T1, T2, FM) case GK_TW_##T1##_##T2: launch_tw<T1, T2, FM>(g, p, stream); return true;
+        GEMM_TW_KERNELS(X)
+#undef X
+        default: return false;
     }
-    static const int allow_b = getenv("MMG_TN_WIDE_B") ? atoi(getenv("MMG_TN_WIDE_B")) : 1;     // 0: the 256-wide tiles off (A/B runs)
-    if (!allow_b && (best == 1 || best == 3)) {      // the 256-wide tiles off: the 384-wide ones or nothing
-        best = narrow <= 96 ? 2 : 0;
-        best_waste = (double)(cdiv(narrow, cfgs[best][0]) * cfgs[best][0]) * (cdiv(wideN, 384) * 384) / ((double)narrow * wideN);
-    }
-    if (best_waste > 1.2) return false;              // badly fitting widths stay on the 128-wide tiles of gemm_bf16.hip
-    const int tn = cfgs[best][0];
-    // N1 > N2 (dW1 = dh^T x of a CNBlock: [4C, C]) runs as its transpose: operands exchanged, tile flushed transposed, bias sums taken
-    // from the B fragments.  Same-run A/B against the mirrored instantiations <384, 192> / <384, 96> (profiles/r02_tn_wide_swap_ab.txt):
-    // equal on the stage-1/2 shapes, 2-3 % faster on 1536 x 384; MMG_TN_WIDE_MIRROR=1 brings the mirrored ones back.
-    static const int mirror = getenv("MMG_TN_WIDE_MIRROR") ? atoi(getenv("MMG_TN_WIDE_MIRROR")) : 0;
-    g.swapped = 0;
-    if (!wide2 && !(mirror && (best == 0 || best == 2))) {
-        const bf16_t* t = g.A; g.A = g.B; g.B = t;
-        int x = g.N1; g.N1 = g.N2; g.N2 = x;
-        x = g.lda; g.lda = g.ldb; g.ldb = x;
-        g.swapped = 1;
-    }
-    if (g.swapped || wide2) {
-        if (best == 0) launch_tw<192, 384>(g, stream);
-        else if (best == 1) launch_tw<256, 256>(g, stream);
-        else if (best == 2) launch_tw<96, 384>(g, stream);
-        else launch_tw<128, 256>(g, stream);
-    } else {
-        if (tn == 96) launch_tw<384, 96>(g, stream); else launch_tw<384, 192>(g, stream);
-    }
-    return true;
 }

@@ -11,6 +11,25 @@ def _rand(shape, dev, scale=1.0, seed=0):
     return (torch.randn(*shape, generator=g) * scale).to(dev).to(torch.bfloat16)
 
 
+# the smallest ragged-M shapes that reach the three 256-row bf16 tiles under default knobs ((16384, 512, 384) and (21760, 384, 384) still take
+# 128-row tiles: the fill rule): the production tiles of ConvNeXt stages 2 / 3 and of BERT, with their 16-pass, read-ahead epilogue
+WIDE_NT_TILES = {(16424, 512, 384): "gemm_nt_kernel<256, 256, 64, 4, 2, 0>", (21800, 384, 384): "gemm_nt_kernel<256, 192, 64, 4, 2, 0>",
+                 (4100, 128, 4096): "gemm_nt_kernel<256, 128, 64, 4, 3, 0>"}
+
+
+def _planned(op, M, N, K):
+    """Kernel instantiation the entry point's host layer names for the shape on this device (mmg_gemm_plan: nothing is launched)."""
+    from mmgclip import _hip
+    text = _hip.load().mmg_gemm_plan(op, M, N, K, 0).decode()
+    assert text, _hip.last_error()
+    return text.split(" grid=")[0]
+
+
+def _assert_reaches_its_tile(M, N, K):
+    if (M, N, K) in WIDE_NT_TILES:          # a later change of the selection rules must fail here, not silently skip the tile
+        assert _planned(0, M, N, K) == WIDE_NT_TILES[(M, N, K)]
+
+
 def test_nt_integer_exact_asymmetric(dev):
     """Small-integer operands are exact in bf16/fp32: catches any fragment/layout transposition bit-exactly."""
     from mmgclip import linalg
@@ -23,9 +42,11 @@ def test_nt_integer_exact_asymmetric(dev):
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 96, 96), (384, 384, 96), (512, 768, 3072), (300, 200, 160),
-                                   (64, 512, 768), (1024, 2304, 768), (37, 512, 768), (4096, 192, 768), (4100, 768, 384), (4353, 512, 1536)])
+                                   (64, 512, 768), (1024, 2304, 768), (37, 512, 768), (4096, 192, 768), (4100, 768, 384), (4353, 512, 1536)]
+                         + list(WIDE_NT_TILES))
 def test_nt_plain(dev, M, N, K):
     from mmgclip import linalg
+    _assert_reaches_its_tile(M, N, K)
     a, b = _rand((M, K), dev, 1.0, 1), _rand((N, K), dev, 0.05, 2)
     ref = a.float() @ b.float().t()
     c32 = linalg.gemm_nt(a, b, out_dtype=torch.float32)
@@ -34,57 +55,87 @@ def test_nt_plain(dev, M, N, K):
     np.testing.assert_allclose(c16.float().cpu().numpy(), ref.cpu().numpy(), rtol=1e-2, atol=1e-2)
 
 
-@pytest.mark.parametrize("M,N,K", [(512, 384, 96), (4200, 512, 384)])      # second shape: the 256x256 tile path
-def test_nt_epilogues(dev, M, N, K):
+NT_EPILOGUE_ARMS = ("gelu", "scale_residual", "dgelu_f32", "dgelu_bf16", "dgelu_only", "gelu_daux_mul_aux", "relu")
+# arms of test_nt_epilogues that are known to miss their bar on a shape: they run in test_nt_epilogues_known_failing_arm, strict xfail
+NT_EPILOGUE_KNOWN_FAILING = {
+    (4100, 128, 4096): {"dgelu_bf16": "EPI_DGELU, bf16 data gradient, on gemm_nt_kernel<256, 128, 64, 4, 3, 0>: with K = 4096 |a b^T| reaches 32 and the "
+                                      "polynomial GELU' (|error| <= 5.2e-4, csrc/common.h) times it passes atol = 1e-2 where GELU' is small"},
+}
+
+
+def _nt_epilogue_arms(dev, M, N, K, arms):
+    """The epilogue checks of test_nt_epilogues, those named in `arms`."""
     from mmgclip import linalg
     a, b = _rand((M, K), dev, 1.0, 3), _rand((N, K), dev, 0.1, 4)
     bias = torch.randn(N, device=dev)
     cs = torch.rand(N, device=dev) + 0.5
     res = _rand((M, N), dev, 1.0, 5)
     pre = a.float() @ b.float().t() + bias
-    # GELU forward with saved pre-activation
-    h = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    y = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU, aux_out=h)
-    np.testing.assert_allclose(h.float().cpu().numpy(), pre.cpu().numpy(), rtol=1e-2, atol=1e-2)
-    np.testing.assert_allclose(y.float().cpu().numpy(), torch.nn.functional.gelu(pre).cpu().numpy(), rtol=1e-2, atol=1e-2)
-    # bias + layer scale + residual (ConvNeXt block tail)
-    y = linalg.gemm_nt(a, b, bias=bias, colscale=cs, residual=res, out_dtype=torch.float32)
-    np.testing.assert_allclose(y.cpu().numpy(), (pre * cs + res.float()).cpu().numpy(), rtol=1e-4, atol=1e-3)
-    # GELU backward: (a b^T) * gelu'(h)
+    if "gelu" in arms:              # GELU forward with saved pre-activation
+        h = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        y = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU, aux_out=h)
+        np.testing.assert_allclose(h.float().cpu().numpy(), pre.cpu().numpy(), rtol=1e-2, atol=1e-2)
+        np.testing.assert_allclose(y.float().cpu().numpy(), torch.nn.functional.gelu(pre).cpu().numpy(), rtol=1e-2, atol=1e-2)
+    if "scale_residual" in arms:    # bias + layer scale + residual (ConvNeXt block tail)
+        y = linalg.gemm_nt(a, b, bias=bias, colscale=cs, residual=res, out_dtype=torch.float32)
+        np.testing.assert_allclose(y.cpu().numpy(), (pre * cs + res.float()).cpu().numpy(), rtol=1e-4, atol=1e-3)
     hh = _rand((M, N), dev, 1.0, 6)
-    act = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    y = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU, aux_in=hh, aux_out=act, out_dtype=torch.float32)
-    np.testing.assert_allclose(act.float().cpu().numpy(), torch.nn.functional.gelu(hh.float()).cpu().numpy(), rtol=1e-2, atol=1e-2)
     x = hh.float().requires_grad_(True)
     torch.nn.functional.gelu(x).sum().backward()
-    np.testing.assert_allclose(y.cpu().numpy(), ((a.float() @ b.float().t()) * x.grad).cpu().numpy(), rtol=1e-3, atol=1e-3)
+    if {"dgelu_f32", "dgelu_only"} & set(arms):     # GELU backward: (a b^T) * gelu'(h)
+        act = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        y = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU, aux_in=hh, aux_out=act, out_dtype=torch.float32)
+    if "dgelu_f32" in arms:
+        np.testing.assert_allclose(act.float().cpu().numpy(), torch.nn.functional.gelu(hh.float()).cpu().numpy(), rtol=1e-2, atol=1e-2)
+        np.testing.assert_allclose(y.cpu().numpy(), ((a.float() @ b.float().t()) * x.grad).cpu().numpy(), rtol=1e-3, atol=1e-3)
     # the same with a bf16 data gradient, as the towers call it: GELU / GELU' by the exp-free polynomials (2^-11; the output rounds at 2^-9)
-    act2 = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    y2 = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU, aux_in=hh, aux_out=act2)
-    assert y2.dtype == torch.bfloat16
-    np.testing.assert_allclose(y2.float().cpu().numpy(), ((a.float() @ b.float().t()) * x.grad).cpu().numpy(), rtol=1e-2, atol=1e-2)
-    np.testing.assert_allclose(act2.float().cpu().numpy(), torch.nn.functional.gelu(hh.float()).cpu().numpy(), rtol=1e-2, atol=1e-2)
-    # epilogue 5: GELU' alone (callers that kept GELU(h) from the forward) - bit-identical to epilogue 2's data gradient, fp32 and bf16
-    y5 = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU_ONLY, aux_in=hh, out_dtype=torch.float32)
-    assert torch.equal(y5, y)
-    assert torch.equal(linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU_ONLY, aux_in=hh), y2)
-    # epilogue 6 (round 4): GELU forward whose side output is GELU'(pre-activation); epilogue 7: multiply by that saved tensor - together the
-    # data gradient of epilogue 5 up to the bf16 rounding of the saved derivative (computed from the fp32 pre-activation here, from bf16(h) there)
-    dsave = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    y6 = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU_DAUX, aux_out=dsave)
-    assert torch.equal(y6, linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU))
-    xp = pre.clone().requires_grad_(True)
-    torch.nn.functional.gelu(xp).sum().backward()
-    np.testing.assert_allclose(dsave.float().cpu().numpy(), xp.grad.cpu().numpy(), rtol=2 ** -8, atol=6e-4)
-    y7 = linalg.gemm_nt(a, b, epi=linalg.EPI_MUL_AUX, aux_in=dsave, out_dtype=torch.float32)
-    np.testing.assert_allclose(y7.cpu().numpy(), ((a.float() @ b.float().t()) * dsave.float()).cpu().numpy(), rtol=1e-4, atol=1e-3)
-    y7b = linalg.gemm_nt(a, b, epi=linalg.EPI_MUL_AUX, aux_in=dsave)
-    np.testing.assert_allclose(y7b.float().cpu().numpy(), ((a.float() @ b.float().t()) * xp.grad).cpu().numpy(), rtol=1e-2, atol=1e-2)
-    # ReLU pair
-    y = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_RELU, out_dtype=torch.float32)
-    np.testing.assert_allclose(y.cpu().numpy(), torch.relu(pre).cpu().numpy(), rtol=1e-4, atol=1e-3)
-    y = linalg.gemm_nt(a, b, epi=linalg.EPI_DRELU, aux_in=hh, out_dtype=torch.float32)
-    np.testing.assert_allclose(y.cpu().numpy(), ((a.float() @ b.float().t()) * (hh.float() > 0)).cpu().numpy(), rtol=1e-4, atol=1e-3)
+    if {"dgelu_bf16", "dgelu_only"} & set(arms):
+        act2 = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        y2 = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU, aux_in=hh, aux_out=act2)
+        assert y2.dtype == torch.bfloat16
+    if "dgelu_bf16" in arms:
+        np.testing.assert_allclose(y2.float().cpu().numpy(), ((a.float() @ b.float().t()) * x.grad).cpu().numpy(), rtol=1e-2, atol=1e-2)
+        np.testing.assert_allclose(act2.float().cpu().numpy(), torch.nn.functional.gelu(hh.float()).cpu().numpy(), rtol=1e-2, atol=1e-2)
+    if "dgelu_only" in arms:        # epilogue 5: GELU' alone (callers that kept GELU(h) from the forward) - bit-identical to epilogue 2's data gradient, fp32 and bf16
+        y5 = linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU_ONLY, aux_in=hh, out_dtype=torch.float32)
+        assert torch.equal(y5, y)
+        assert torch.equal(linalg.gemm_nt(a, b, epi=linalg.EPI_DGELU_ONLY, aux_in=hh), y2)
+    if "gelu_daux_mul_aux" in arms:
+        # epilogue 6 (round 4): GELU forward whose side output is GELU'(pre-activation); epilogue 7: multiply by that saved tensor - together the
+        # data gradient of epilogue 5 up to the bf16 rounding of the saved derivative (computed from the fp32 pre-activation here, from bf16(h) there)
+        dsave = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        y6 = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU_DAUX, aux_out=dsave)
+        assert torch.equal(y6, linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_GELU))
+        xp = pre.clone().requires_grad_(True)
+        torch.nn.functional.gelu(xp).sum().backward()
+        np.testing.assert_allclose(dsave.float().cpu().numpy(), xp.grad.cpu().numpy(), rtol=2 ** -8, atol=6e-4)
+        y7 = linalg.gemm_nt(a, b, epi=linalg.EPI_MUL_AUX, aux_in=dsave, out_dtype=torch.float32)
+        np.testing.assert_allclose(y7.cpu().numpy(), ((a.float() @ b.float().t()) * dsave.float()).cpu().numpy(), rtol=1e-4, atol=1e-3)
+        y7b = linalg.gemm_nt(a, b, epi=linalg.EPI_MUL_AUX, aux_in=dsave)
+        np.testing.assert_allclose(y7b.float().cpu().numpy(), ((a.float() @ b.float().t()) * xp.grad).cpu().numpy(), rtol=1e-2, atol=1e-2)
+    if "relu" in arms:              # ReLU pair
+        y = linalg.gemm_nt(a, b, bias=bias, epi=linalg.EPI_RELU, out_dtype=torch.float32)
+        np.testing.assert_allclose(y.cpu().numpy(), torch.relu(pre).cpu().numpy(), rtol=1e-4, atol=1e-3)
+        y = linalg.gemm_nt(a, b, epi=linalg.EPI_DRELU, aux_in=hh, out_dtype=torch.float32)
+        np.testing.assert_allclose(y.cpu().numpy(), ((a.float() @ b.float().t()) * (hh.float() > 0)).cpu().numpy(), rtol=1e-4, atol=1e-3)
+
+
+# (4200, 512, 384): 128 x 128 tiles with a ragged last row of tiles (its 34 tiles of 256 x 256 would fill 13 % of a round of CUs: the fill rule)
+@pytest.mark.parametrize("M,N,K", [(512, 384, 96), (4200, 512, 384)] + list(WIDE_NT_TILES))
+def test_nt_epilogues(dev, M, N, K):
+    _assert_reaches_its_tile(M, N, K)
+    _nt_epilogue_arms(dev, M, N, K, [arm for arm in NT_EPILOGUE_ARMS if arm not in NT_EPILOGUE_KNOWN_FAILING.get((M, N, K), {})])
+
+
+@pytest.mark.parametrize("M,N,K,arm", [pytest.param(*shape, arm, marks=pytest.mark.xfail(strict=True, reason=why))
+                                       for shape, arms in NT_EPILOGUE_KNOWN_FAILING.items() for arm, why in arms.items()])
+def test_nt_epilogues_known_failing_arm(dev, M, N, K, arm):
+    """A kernel finding, kept visible: the arm of test_nt_epilogues that misses its (unchanged) bar on this shape.  Measured on the MI355X,
+    (4100, 128, 4096), dgelu_bf16: 2 of 524 800 elements of the bf16 data gradient miss rtol = atol = 1e-2, the worst by |error| = 1.1027e-2 against a
+    bar of 1.0574e-2 at |reference| = 5.7e-2 (the same against an fp64 reference); every other arm of this shape, and every arm of the other
+    shapes, holds.  A model of the kernel's arithmetic in torch (fp32 product times the polynomial, rounded to bf16) gives the same two
+    elements: |a b^T| = 23 there times the polynomial's documented error is the whole of it."""
+    _nt_epilogue_arms(dev, M, N, K, [arm])
 
 
 def test_nt_gelu_epilogues_on_a_bert_ffn_shape_against_erf_gelu(dev):
@@ -243,13 +294,11 @@ def test_nt_fp8_rejects_bad_k(dev):
 
 
 # ---- wide-tile weight-gradient kernel (gemm_tn_wide.hip: M >= 65536, widths that fit 96/192 x 384) ---------------------------
-@pytest.mark.parametrize("mirror", ["0", "1"])
-def test_tn_wide_integer_exact_asymmetric(dev, mirror, monkeypatch):
-    """Every configuration of the 8-wave kernel on exact small integers (fp32 sums stay exact): 192x384, 96x384 tiles, N1 > N2 shapes
-    both as the exchanged-operand / transposed-flush form (default) and on the mirrored 384x192 / 384x96 instantiations
-    (MMG_TN_WIDE_MIRROR=1), several tiles per side, asymmetric operands (a transposed or mis-swizzled fragment cannot pass)."""
+def test_tn_wide_integer_exact_asymmetric(dev):
+    """Every configuration of the 8-wave kernel on exact small integers (fp32 sums stay exact): 192x384, 96x384, 256x256, 128x256 tiles, N1 > N2
+    shapes in the exchanged-operand / transposed-flush form, several tiles per side, asymmetric operands (a transposed or mis-swizzled
+    fragment cannot pass)."""
     from mmgclip import linalg
-    monkeypatch.setenv("MMG_TN_WIDE_MIRROR", mirror)
     for M, N1, N2 in ((65536, 192, 384), (65536 + 32, 384, 192), (70000, 96, 384), (65568, 384, 96), (66000, 384, 768), (65536, 768, 384),
                       (65536, 128, 512), (65600, 512, 128), (66000, 256, 1024), (65536 + 64, 1024, 256), (65536, 512, 2048)):   # ConvNeXt-B widths
         g = torch.Generator().manual_seed(M + N1)
@@ -438,3 +487,63 @@ def test_tn_fp8(dev, monkeypatch, M, N1, N2, e5, wide):
     ref = 1.0 + 0.25 * (a.t() @ b)
     np.testing.assert_allclose(out.cpu().numpy(), ref.float().cpu().numpy(), rtol=5e-4, atol=5e-4 * M ** 0.5)
     np.testing.assert_allclose(cs.cpu().numpy(), (2.0 + 0.25 * a.sum(0)).float().cpu().numpy(), rtol=5e-4, atol=5e-4 * M ** 0.5)
+
+
+# ---- the kernel that runs is the kernel the host layer planned ---------------------------------------------------------------------------------
+NT_BF16, NT_FP8, NT_FP8_BWD_E5M2, NT_FP8_BWD_E4M3, TN_BF16, TN_FP8_E5M2, TN_FP8_E4M3 = range(7)          # `op` of mmg_gemm_plan
+PLANNED = ([(NT_BF16,) + s for s in [(256, 128, 64), (300, 200, 160), (64, 512, 768), (256, 96, 96), (256, 96, 128)] + list(WIDE_NT_TILES)]
+           + [(NT_FP8,) + s for s in [(256, 256, 128), (4096, 256, 512), (4100, 384, 256)]]
+           + [(op,) + s for s in [(640, 384, 128), (4096, 256, 128)] for op in (NT_FP8_BWD_E5M2, NT_FP8_BWD_E4M3)]
+           + [(TN_BF16,) + s for s in [(256, 128, 128), (32768, 128, 256), (32768, 256, 128), (65536, 192, 384), (65536, 384, 192), (65536, 96, 384),
+                                       (65536, 128, 512), (65536, 256, 1024), (65599, 200, 392)]]
+           + [(op,) + s for s in [(384, 128, 256), (8192, 256, 256), (8191, 256, 256)] for op in (TN_FP8_E5M2, TN_FP8_E4M3)])
+
+
+@pytest.mark.parametrize("op,M,N,K", PLANNED)
+def test_launched_kernel_is_the_planned_one(dev, op, M, N, K):
+    """One small shape per instantiation of the five GEMM entry points: with kernel notes on, the name the launcher records is the name in
+    mmg_gemm_plan's string, and the result agrees with fp64 (tolerances of the value tests above), so the launch is a real one.  For the
+    weight-gradient ops N, K stand for N1, N2."""
+    from mmgclip import _hip
+    from mmgclip import linalg as L
+    lib = _hip.load()
+    want = _planned(op, M, N, K)
+    if (op, M, N, K) == (TN_BF16, 65599, 200, 392):
+        assert want == "gemm_tn_kernel<1, 1, 64>"                       # widths the wide tiles fit badly stay on the 128-wide ones
+    if (op, M, N, K) == (TN_BF16, 65536, 384, 192):
+        assert " swapped=1" in lib.mmg_gemm_plan(op, M, N, K, 0).decode()
+    g = torch.Generator().manual_seed(17)
+    f8a = torch.float8_e5m2 if op in (NT_FP8_BWD_E5M2, TN_FP8_E5M2) else torch.float8_e4m3fn
+    lib.mmg_set_kernel_notes(1)
+    try:
+        if op == NT_BF16:
+            a, b = _rand((M, K), dev, 1.0, 1), _rand((N, K), dev, 0.05, 2)
+            out = L.gemm_nt(a, b, out_dtype=torch.float32)
+            ran = lib.mmg_last_kernel().decode()
+            np.testing.assert_allclose(out.double().cpu().numpy(), (a.double() @ b.double().t()).cpu().numpy(), rtol=1e-4, atol=1e-4 * K ** 0.5)
+        elif op <= NT_FP8_BWD_E4M3:
+            a8, b8 = _q8(torch.randn(M, K, generator=g), f8a).to(dev), _q8(torch.randn(N, K, generator=g), torch.float8_e4m3fn).to(dev)
+            if op == NT_FP8:
+                out = L.gemm_nt_fp8(a8, b8, out_kind=L.OUT_F32)
+            else:
+                out = L.gemm_nt_fp8_bwd(a8, b8, a_e5m2=op == NT_FP8_BWD_E5M2, out_kind=L.OUT_F32)
+            ran = lib.mmg_last_kernel().decode()
+            ref = a8.view(f8a).float().double() @ b8.view(torch.float8_e4m3fn).float().double().t()
+            assert float((out.double() - ref).abs().max()) <= 1e-4 * float(ref.abs().max())
+        else:
+            out = torch.ones(N, K, device=dev)
+            if op == TN_BF16:
+                a, b = _rand((M, N), dev, 1.0, 7), _rand((M, K), dev, 1.0, 8)
+                L.gemm_tn_acc(a, b, out)
+                tol = 2e-4
+            else:
+                a8, b8 = _q8(torch.randn(M, N, generator=g), f8a).to(dev), _q8(torch.randn(M, K, generator=g), torch.float8_e4m3fn).to(dev)
+                L.gemm_tn_fp8_acc(a8, b8, out, a_e5m2=op == TN_FP8_E5M2)
+                a, b = a8.view(f8a).float(), b8.view(torch.float8_e4m3fn).float()
+                tol = 5e-4
+            ran = lib.mmg_last_kernel().decode()
+            ref = 1.0 + a.double().t() @ b.double()
+            np.testing.assert_allclose(out.double().cpu().numpy(), ref.cpu().numpy(), rtol=tol, atol=tol * M ** 0.5)
+    finally:
+        lib.mmg_set_kernel_notes(0)
+    assert ran == want
