@@ -396,7 +396,8 @@ int mmg_bn_bwd_apply(const void* dy, const void* x, const void* out, const float
 
 /* ctx[B*S,Hd] = per-head softmax(Q K^T * scale + key mask) V with qkv = [B*S, q|k|v] bf16 (head h at columns h*64
  * of each third); mask int64 [B,S] (1 attend / 0 pad, nullable); lse fp32 [B,heads,S] (nullable) for the backward.
- * head_dim 64, S <= 512.  Replaces HF BertSelfAttention (mmgclip/networks/encoder.py:156). */
+ * head_dim 64, S <= 512.  The mask may be any 0/1 pattern (not only a right-padded prefix); the result for a sequence whose
+ * mask row is all zero is unspecified.  Replaces HF BertSelfAttention (mmgclip/networks/encoder.py:156). */
 int mmg_attention_fwd(const void* qkv, int ld, const long long* mask, void* ctx, int ldc, float* lse, int B, int S,
                       int heads, int Hd, float scale, mmg_stream_t stream);
 /* dqkv (same layout as qkv) from dctx; recomputes probabilities from lse.  S <= 256. */

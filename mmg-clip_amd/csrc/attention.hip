@@ -666,7 +666,12 @@ __global__ __launch_bounds__(256, 2) void attn_flash_fwd_kernel(const AttArgs a)
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float pv = att_exp2(fmaf(sc[rb][t][r], c2, -mn));
+                    float pv = att_exp2(fmaf(sc[rb][t][r], c2, -mn));
+                    // A key mask can hide EVERY key a row has seen so far (left padding of 64 keys or more).  Then mn is the rounded
+                    // product ATT_NEG * c2 and the fma returns that rounding's residual, up to ~1e21 of either sign: exp2 of it is
+                    // +inf and the row ends as NaN.  So a masked key's probability is selected, as in attn_flash_dq_kernel.  Without a
+                    // key mask the only ATT_NEG scores are past S in the last tile, which always holds an attended key: loop unchanged.
+                    if constexpr (MASK) pv = sc[rb][t][r] == ATT_NEG ? 0.f : pv;
                     sc[rb][t][r] = pv;
                     ps += pv;
                 }
