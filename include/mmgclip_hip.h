@@ -226,6 +226,21 @@ int mmg_layerscale_finalize(const float* W2, const float* b2, const float* gamma
 int mmg_grad_relayout(const float* src, float* dst, int mode, int R, int CI, int KH, int KW, int ld_src,
                       mmg_stream_t stream);
 
+/* ---- stochastic depth, "row" mode (csrc/stochastic_depth.hip) ------------------------------------------------
+ * torchvision CNBlock.stochastic_depth = StochasticDepth(p, "row") of the ConvNeXt behind mmgclip/networks/encoder.py:53 (the reference runs
+ * it frozen, where it is the identity).  A block's dropped samples are not computed at all: the images of a micro-batch are reordered so that
+ * the kept ones are a prefix, and the block's kernels run on that prefix.  Activations are bf16 [n, rows, C]; C % 8 == 0 and 16-byte aligned
+ * pointers (16-byte accesses, 64-bit offsets); every element touched is written once, no atomics.  Additive entry points: mmg_abi_version()
+ * stays 5.
+ * mmg_image_swap: IN PLACE, exchange image pairs[p][0] with image pairs[p][1] for p < k.  pairs: device int32 [k][2]; pairs_host: the same
+ *   table in host memory - it is what is validated before the launch (every index inside 0 .. n-1, no image in two pairs).  k = 0: no launch.
+ * mmg_image_copy: dst[first .. first+count) = src[first .. first+count) (whole images; src != dst).  count = 0: no launch. */
+int mmg_image_swap(void* x, const int* pairs, const int* pairs_host, int k, int n, long long rows, int C, mmg_stream_t stream);
+int mmg_image_copy(const void* src, void* dst, int first, int count, int n, long long rows, int C, mmg_stream_t stream);
+/* dst += alpha * src (fp32 [n]).  With stochastic depth the layer scale the kernels see is gamma / (1 - p): mmg_layerscale_finalize then
+ * yields d/d(that product) into a temporary, and this folds it into the gradient of gamma with alpha = 1 / (1 - p). */
+int mmg_scaled_add_f32(float* dst, const float* src, float alpha, long long n, mmg_stream_t stream);
+
 /* Inverted dropout on fp32 (projection heads: mmgclip/networks/projection.py:50,59,91,98); keep = uint8 mask. */
 int mmg_dropout_fwd(const float* x, float* y, void* keep, long long n, float p, long long seed, mmg_stream_t stream);
 int mmg_dropout_bwd(const float* dy, const void* keep, float* dx, long long n, float p, mmg_stream_t stream);

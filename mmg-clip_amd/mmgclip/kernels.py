@@ -2,6 +2,7 @@
 
 Shapes follow the device layout: activations are bf16 row-major [rows, channels] (NHWC flattened for images).
 """
+import ctypes
 import os
 
 import torch
@@ -162,6 +163,42 @@ def avgpool_bwd(dy, n, HW, C, out=None):
     return dx
 
 
+def _images(x, n):
+    """(rows, C) of a bf16 [n * rows, C] activation holding n images."""
+    assert x.dtype == BF16 and x.dim() == 2 and x.is_contiguous() and n > 0 and x.shape[0] % n == 0, "bf16 [n * rows, C], contiguous"
+    _hip.require_gpu(x)
+    return x.shape[0] // n, x.shape[1]
+
+
+def image_swap_(x, n, pairs_dev, pairs_host, k, offset=0):
+    """x bf16 [n * rows, C]: exchange, IN PLACE, the images of pairs offset .. offset + k - 1 of a pair table (stochastic depth,
+    convnext_sd.schedule).  pairs_dev: int32 [*, 2] on the device; pairs_host: the same table as a ctypes int array - what the library
+    validates before it launches."""
+    rows, C = _images(x, n)
+    if k:
+        assert pairs_dev.dtype == torch.int32 and pairs_dev.is_contiguous() and 2 * (offset + k) <= pairs_dev.numel() == len(pairs_host)
+    call("mmg_image_swap", ptr(x), ctypes.c_void_p(pairs_dev.data_ptr() + 8 * offset) if k else None,
+         ctypes.c_void_p(ctypes.addressof(pairs_host) + 8 * offset) if k else None, k, n, rows, C, stream())
+    return x
+
+
+def image_copy(src, dst, n, first, count):
+    """dst's images first .. first + count - 1 = src's (both bf16 [n * rows, C])."""
+    rows, C = _images(src, n)
+    assert dst.shape == src.shape and dst.dtype == BF16 and dst.is_contiguous()
+    _hip.require_gpu(dst)
+    call("mmg_image_copy", ptr(src), ptr(dst), first, count, n, rows, C, stream())
+    return dst
+
+
+def scaled_add_(dst, src, alpha):
+    """dst += alpha * src (fp32, contiguous, same size)."""
+    assert dst.dtype == src.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous() and dst.numel() == src.numel()
+    _hip.require_gpu(dst, src)
+    call("mmg_scaled_add_f32", ptr(dst), ptr(src), float(alpha), dst.numel(), stream())
+    return dst
+
+
 def view_pool_fwd(feat, offsets, S, mode, out=None, argmax=None):
     """feat fp32 [V,C], offsets int32 [S+1] on the device -> (out fp32 [S,C], argmax int32 [S,C] or None); mode 0 = mean, 1 = max."""
     V, C = feat.shape
@@ -279,11 +316,14 @@ def cnblock_pack(w1, w2, gamma=None, backward=False):
 
 
 def cnblock_mlp_fwd(xd, ln_w, ln_b, eps, packed, b1, b2, gamma, residual, want_hpre=False, want_stats=False, want_xln=False, want_gact=False,
-                    hpre_kind=0):
+                    hpre_kind=0, out=None):
     """-> y, hpre, mean, rstd (and, with want_xln, the LayerNorm output as a fifth value; with want_gact, GELU(hidden) - the activation as
-    the second GEMM consumed it, bf16 [M,4C] - as the last value).  hpre_kind = 1 (with want_gact): `hpre` holds GELU'(hidden)."""
+    the second GEMM consumed it, bf16 [M,4C] - as the last value).  hpre_kind = 1 (with want_gact): `hpre` holds GELU'(hidden).
+    out: bf16 [M,C] contiguous that receives y (not `residual`'s memory)."""
     M, C = xd.shape
-    y = torch.empty_like(xd)
+    if out is not None:
+        assert out.shape == xd.shape and out.dtype == BF16 and out.is_contiguous() and out.data_ptr() != residual.data_ptr()
+    y = out if out is not None else torch.empty_like(xd)
     hpre = torch.empty(M, 4 * C, device=xd.device, dtype=BF16) if want_hpre else None
     xln = torch.empty(M, C, device=xd.device, dtype=BF16) if (want_xln and want_hpre) else None
     gact = torch.empty(M, 4 * C, device=xd.device, dtype=BF16) if (want_gact and want_hpre) else None

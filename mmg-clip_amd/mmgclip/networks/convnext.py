@@ -9,7 +9,9 @@ Permute, LayerNorm, Linear C->4C, GELU, Linear 4C->C, Permute) * layer_scale + r
 capability (north star) and is checked against oracle/encoders_oracle.py.
 
 Parameter names/shapes follow torchvision (`features.{i}.{j}.block.{k}.weight`, `layer_scale` ...) so a torchvision
-state dict loads unchanged.  Stochastic depth is not applied (p = 0).
+state dict loads unchanged.  Stochastic depth (torchvision's `StochasticDepth(p, "row")` at the end of every CNBlock) is off by default
+(`stochastic_depth_prob=0`); with a rate, a training-mode forward drops whole samples per block and never computes them: the schedule
+is convnext_sd.py's, the image moves are csrc/stochastic_depth.hip's.
 
 Data layout on the MI355X: activations are bf16 [n*H*W, C] (NHWC flattened), so every pointwise Linear is a plain
 row-major GEMM and LayerNorm reads contiguous rows; the 2x2/4x4 stride=kernel convolutions become GEMMs on patchified
@@ -24,6 +26,7 @@ column as torch's convolutions do; the forward records each stage's map size and
 gradient from mmg_layernorm_bwd).  `forward` also takes a list of [Cin, H_i, W_i] images of different sizes: grouped by size in order of first
 appearance (`group_by_size`), each group in micro-batches of its own, features and gradients routed back in input order.
 """
+import ctypes
 import os
 
 import torch
@@ -34,6 +37,7 @@ from .. import kernels as K
 from .. import linalg as L
 from .._hip import call, ptr, stream
 from ..params import backward_finished, last_backward
+from . import convnext_sd as SD
 from .convnext_plan import BlockSaved, Knobs, decide_saves, fused_forward, plan_block, saving_form
 from .tower import Tower, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
 
@@ -99,8 +103,13 @@ class ConvNextTower(Tower):
     """pixels fp32 [n, Cin, H, W] in [0,1] (scale16=True applies the reference's 16-bit scaling) -> features [n, dims[-1]]."""
 
     def __init__(self, variant="tiny", in_chans=1, scale16=True, micro_batch=64, fused_mlp=None, checkpoint=False, fp8=False,
-                 fp8_min_channels=None):
+                 fp8_min_channels=None, stochastic_depth_prob=0.0):
         super().__init__()
+        # torchvision's recipes: 0.1 (tiny), 0.4 (small), 0.5 (base); block b of B drops a sample with p_b = rate * b / (B - 1).  Acts in
+        # training mode only, with or without gradients; 0 is the path without it, bit for bit
+        self.stochastic_depth_prob = SD.check_rate(stochastic_depth_prob)
+        self.next_drop_seed = None          # tests: force the seed of the next forward that applies stochastic depth
+        self._drop_seeds = SD.DropSeeds()
         self.variant, self.in_chans, self.scale16, self.micro_batch = variant, in_chans, scale16, micro_batch
         # narrow stages (C <= 256) run the CNBlock MLP as one fused launch; MMG_FUSED_MLP=0 keeps the GEMM pair
         self.fused_mlp = (os.environ.get("MMG_FUSED_MLP", "1") != "0") if fused_mlp is None else bool(fused_mlp)
@@ -147,6 +156,19 @@ class ConvNextTower(Tower):
         """Gradient view (arena) of parameter `leaf` of module `mod`."""
         return self._arena.g(self._pname[id(mod)] + "." + leaf)
 
+    def stochastic_depth_active(self):
+        return self.training and self.stochastic_depth_prob > 0.0
+
+    def reseed_stochastic_depth(self, seed=None):
+        """Restart the tower's private seed stream from (seed, rank); seed=None: the last `seeding()` call's seed (convnext_sd.DropSeeds)."""
+        self._drop_seeds.reseed(seed)
+
+    def _working_copy_key(self):
+        """(+ whether stochastic depth acts, and at which rate: the copies that bake the layer scale in hold gamma / (1 - p_b) then, and
+        eval() after train() must not read those)"""
+        active = self.stochastic_depth_active()
+        return self._arena.version(), active, self.stochastic_depth_prob if active else 0.0
+
     def knobs(self):
         return Knobs(self.fp8, self.fp8_min_channels, self.fp8_bwd, self.fused_mlp, self.fused_bwd_saved_h, self.bwdw, _fused_save_maxc())
 
@@ -159,11 +181,20 @@ class ConvNextTower(Tower):
         f = self.model.features
         plan = self.plan = self._plan_blocks()
         wc = {"stem.w": K.cast_bf16(conv_weight_rows(f[0][0].weight.data))}          # [C0, Cin, 4, 4] -> [C0, kp]
+        # stochastic depth: a kept sample's branch is scaled by s_b = 1 / (1 - p_b), the same for every kept sample of block b, so the
+        # kernels simply read gamma * s_b as their layer scale (".gamma": the vector the forward passes, baked into .w2gt / .w2gt8 /
+        # .mlpb / .bwdw below); None: stochastic depth does not act and ".gamma" is the parameter itself
+        scales = wc["sd.scales"] = SD.scales(self.stochastic_depth_prob, self.depths) if self.stochastic_depth_active() else None
+        b = 0
         for si, p in enumerate(plan):
             C = p.C
             for bi, blk in enumerate(f[1 + 2 * si]):
                 key = f"{si}.{bi}"
                 w1, w2, gamma = blk.block[3].weight.data, blk.block[5].weight.data, blk.layer_scale.data.reshape(C)
+                if scales is not None and scales[b] != 1.0:
+                    gamma = gamma * scales[b]
+                wc[key + ".gamma"] = gamma
+                b += 1
                 wc[key + ".w49"] = blk.block[0].weight.data.reshape(C, 49).t().contiguous()
                 wc[key + ".w1"] = K.cast_bf16(w1)                                            # [4C, C]
                 wc[key + ".w1t"] = K.transpose_cast_bf16(w1)                                 # [C, 4C]
@@ -199,21 +230,22 @@ class ConvNextTower(Tower):
     def _saving(self, p, dec, M):
         return saving_form(p, dec, M, self.save_dgelu) if dec is not None else (None, None, False, False)
 
-    def _fwd_fused(self, x, d, blk, key, p, dec):
+    def _fwd_fused(self, x, d, blk, key, p, dec, out=None):
         """LN + Linear + GELU + Linear + layer scale + residual in one launch.  A GEMM-pair backward (C = 384 by default) gets its optional
         tensors from the forward's registers: the LayerNorm output as one [M,C] store instead of a LayerNorm pass over d in the backward,
         GELU(hidden) as the second GEMM consumed it."""
         bwd, aux_kind, keep_ln, keep_g = self._saving(p, dec, d.shape[0])
         keep = aux_kind is not None
         outs = K.cnblock_mlp_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, self._wc[key + ".mlp"],
-                                 blk.block[3].bias.data, blk.block[5].bias.data, blk.layer_scale.data.reshape(p.C), x,
-                                 want_hpre=keep, want_stats=keep, want_xln=keep_ln, want_gact=keep_g, hpre_kind=1 if aux_kind == "dgelu" else 0)
+                                 blk.block[3].bias.data, blk.block[5].bias.data, self._wc[key + ".gamma"], x,
+                                 want_hpre=keep, want_stats=keep, want_xln=keep_ln, want_gact=keep_g, hpre_kind=1 if aux_kind == "dgelu" else 0,
+                                 out=out)
         xn, hpre, mean, rstd = outs[:4]
         if dec is None:
             return xn, None
         return xn, BlockSaved(x, d, mean, rstd, hpre, aux_kind, outs[4] if keep_ln else None, outs[-1] if keep_g else None, bwd)
 
-    def _fwd_gemm(self, x, d, blk, key, p, dec):
+    def _fwd_gemm(self, x, d, blk, key, p, dec, out=None):
         """LayerNorm, then the two pointwise GEMMs with GELU / layer scale + residual in their epilogues; bf16 or (fp8 blocks) e4m3 operands,
         fp32 accumulate.  The 4C-wide side output (the pre-activation, or GELU' of it) is bf16 in both."""
         C, wc, save = p.C, self._wc, dec is not None
@@ -224,25 +256,36 @@ class ConvNextTower(Tower):
             ln, mean, rstd = K.layernorm_fwd_fp8(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
             g = L.gemm_nt_fp8(ln, wc[key + ".w1f8"], bias=blk.block[3].bias.data, aux_out=hpre, epi=epi, out_kind=L.OUT_E4M3,
                               alpha_dev=wc[key + ".s1"][1:])
-            xn = L.gemm_nt_fp8(g, wc[key + ".w2f8"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C),
+            xn = L.gemm_nt_fp8(g, wc[key + ".w2f8"], out=out, bias=blk.block[5].bias.data, colscale=wc[key + ".gamma"],
                                residual=x, alpha_dev=wc[key + ".s2"][1:])
         else:
             ln, mean, rstd = K.layernorm_fwd(d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=save)
             g = L.gemm_nt(ln, wc[key + ".w1"], bias=blk.block[3].bias.data, aux_out=hpre, epi=epi)
-            xn = L.gemm_nt(g, wc[key + ".w2"], bias=blk.block[5].bias.data, colscale=blk.layer_scale.data.reshape(C), residual=x)
+            xn = L.gemm_nt(g, wc[key + ".w2"], out=out, bias=blk.block[5].bias.data, colscale=wc[key + ".gamma"], residual=x)
         if not save:
             return xn, None
         return xn, BlockSaved(x, d, mean, rstd, hpre, aux_kind, ln if keep_ln else None, g if keep_g else None, bwd)
 
     # ---- forward / backward over one micro-batch -----------------------------------------------------------
-    def _forward_mb(self, img, plan, dec):
+    def _forward_mb(self, img, plan, dec, sched=None):
         """plan: the tower's BlockPlans as the recorded forward this pass belongs to read them; dec: that forward's SaveDecision, or None
-        when this pass saves nothing (no gradient wanted, or a checkpointed micro-batch whose forward runs again in the backward)."""
+        when this pass saves nothing (no gradient wanted, or a checkpointed micro-batch whose forward runs again in the backward).
+        sched: this micro-batch's stochastic-depth Schedule (convnext_sd.schedule) or None.  With one, the features leave in the order
+        sched.perm (the caller routes them back), and a block that keeps n_k of the n images runs on the first n_k after the schedule's
+        swaps; its record holds views of that prefix."""
         f, wc = self.model.features, self._wc
         save = dec is not None
         n, _, H, W = img.shape
         h, w_ = H // 4, W // 4
         saved = {"maps": [(h, w_)]}                 # map size per stage: floored at every stride, so the backward reads them back
+        steps = table = None
+        if sched is not None:
+            steps = sched.steps
+            if sched.table:                         # every block's pairs in ONE upload; the host copy is what mmg_image_swap validates
+                host = (ctypes.c_int * len(sched.table))(*sched.table)
+                table = (torch.tensor(sched.table, dtype=torch.int32, device=img.device), host)
+            saved["sd"] = (steps, table)
+        b = 0
         p0 = K.patchify(img, 4, self.kp, self.scale16)
         s0 = L.gemm_nt(p0, wc["stem.w"], bias=f[0][0].bias.data)
         x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
@@ -252,8 +295,23 @@ class ConvNextTower(Tower):
             mlp = self._fwd_fused if fused_forward(p, save) else self._fwd_gemm
             for bi, blk in enumerate(f[1 + 2 * si]):
                 key = f"{si}.{bi}"
-                d = K.dwconv7(x, wc[key + ".w49"], blk.block[0].bias.data, n, h, w_, p.C)
-                x, rec = mlp(x, d, blk, key, p, dec)
+                step = steps[b] if steps is not None else None
+                b += 1
+                if step is None or step.n_k == n:
+                    d = K.dwconv7(x, wc[key + ".w49"], blk.block[0].bias.data, n, h, w_, p.C)
+                    x, rec = mlp(x, d, blk, key, p, dec)
+                elif step.n_k == 0:                 # dropped for every image of this micro-batch: the identity, nothing saved
+                    rec = None
+                else:
+                    # x is the previous layer's fresh output and no record holds it (the stem keeps its own input and statistics, a
+                    # downsample layer its input, a block its input - never its output), so the images may change places in it
+                    K.image_swap_(x, n, *(table or (None, None)), len(step.pairs), step.offset)
+                    n_k, Mk = step.n_k, step.n_k * h * w_
+                    xk, out = x[:Mk], torch.empty_like(x)
+                    d = K.dwconv7(xk, wc[key + ".w49"], blk.block[0].bias.data, n_k, h, w_, p.C)
+                    _, rec = mlp(xk, d, blk, key, p, dec, out=out[:Mk])
+                    K.image_copy(x, out, n, n_k, n - n_k)
+                    x = out
                 if save:
                     saved[key] = rec
             if si < 3:
@@ -337,6 +395,8 @@ class ConvNextTower(Tower):
         f, wc, A = self.model.features, self._wc, self._arena
         n, H, W = saved["shape"]
         maps = saved["maps"]
+        steps, table = saved.get("sd", (None, None))
+        b = sum(self.depths)
         h, w_ = maps[3]
         dx = K.avgpool_bwd(dfeat, n, h * w_, self.dims[-1])
         for si in range(3, -1, -1):
@@ -354,10 +414,23 @@ class ConvNextTower(Tower):
                 blk = f[1 + 2 * si][bi]
                 key = f"{si}.{bi}"
                 rec = saved[key]
-                dd = getattr(self, "_bwd_" + rec.bwd)(dx, rec, blk, key, tmp)
-                K.dwconv7_wgrad(rec.x, dd, tmp[key + ".dw49"], self._g(blk.block[0], "bias"), n, h, w_, C)
-                dx = K.dwconv7(dd, wc[key + ".w49"], None, n, h, w_, C, add=dx, flip=True)
-                del dd
+                b -= 1
+                step = steps[b] if steps is not None else None
+                if step is None or step.n_k == n:
+                    dd = getattr(self, "_bwd_" + rec.bwd)(dx, rec, blk, key, tmp)
+                    K.dwconv7_wgrad(rec.x, dd, tmp[key + ".dw49"], self._g(blk.block[0], "bias"), n, h, w_, C)
+                    dx = K.dwconv7(dd, wc[key + ".w49"], None, n, h, w_, C, add=dx, flip=True)
+                    del dd
+                elif step.n_k:                      # (n_k = 0: dx passes through, the block's parameters get nothing)
+                    # the forward's mirror: the block's backward on the kept prefix, the tail copied through, the swap undone
+                    n_k, Mk = step.n_k, step.n_k * h * w_
+                    dxk, dxn = dx[:Mk], torch.empty_like(dx)
+                    dd = getattr(self, "_bwd_" + rec.bwd)(dxk, rec, blk, key, tmp)
+                    K.dwconv7_wgrad(rec.x, dd, tmp[key + ".dw49"], self._g(blk.block[0], "bias"), n_k, h, w_, C)
+                    K.dwconv7(dd, wc[key + ".w49"], None, n_k, h, w_, C, add=dxk, flip=True, out=dxn[:Mk])
+                    del dd, dxk
+                    K.image_copy(dx, dxn, n, n_k, n - n_k)
+                    dx = K.image_swap_(dxn, n, *(table or (None, None)), len(step.pairs), step.offset)
             if final:
                 self._finalize_stage(tmp, si)
                 if announce:
@@ -385,12 +458,19 @@ class ConvNextTower(Tower):
         (layer scale, conv layouts)."""
         f = self.model.features
         C = self.dims[si]
+        scales = self._wc["sd.scales"]
         for bi, blk in enumerate(f[1 + 2 * si]):
             key = f"{si}.{bi}"
+            # stochastic depth: the kernels ran on gamma_eff = gamma * s_b.  Given gamma_eff, dW2 and db2 come out right; the third result is
+            # d/d(gamma_eff), and d/d(gamma) is s_b times it: through a [C] temporary
+            s = scales[sum(self.depths[:si]) + bi] if scales is not None else 1.0
+            dgamma = self._g(blk, "layer_scale") if s == 1.0 else torch.zeros(C, device=tmp[key + ".dw2raw"].device, dtype=torch.float32)
             call("mmg_layerscale_finalize", ptr(blk.block[5].weight.data), ptr(blk.block[5].bias.data),
-                 ptr(blk.layer_scale.data), ptr(tmp[key + ".dw2raw"]), ptr(tmp[key + ".db2raw"]),
+                 ptr(self._wc[key + ".gamma"]), ptr(tmp[key + ".dw2raw"]), ptr(tmp[key + ".db2raw"]),
                  ptr(self._g(blk.block[5], "weight")), ptr(self._g(blk.block[5], "bias")),
-                 ptr(self._g(blk, "layer_scale")), C, 4 * C, stream())
+                 ptr(dgamma), C, 4 * C, stream())
+            if s != 1.0:
+                K.scaled_add_(self._g(blk, "layer_scale"), dgamma, s)
             call("mmg_grad_relayout", ptr(tmp[key + ".dw49"]), ptr(self._g(blk.block[0], "weight")), 1, C, 1, 7, 7, C,
                  stream())
         if si < 3:
@@ -404,9 +484,10 @@ class ConvNextTower(Tower):
             h, w = h // 2, w // 2
         return h, w
 
-    def forward(self, images):
+    def forward(self, images, sample_ids=None):
         """images: fp32 [n, Cin, H, W] (any H, W >= 32), or a list / tuple of [Cin, H_i, W_i] tensors whose sizes may differ: those are grouped by
-        size (`group_by_size`), every group runs in micro-batches of its own, and row i of the result belongs to images[i]."""
+        size (`group_by_size`), every group runs in micro-batches of its own, and row i of the result belongs to images[i].
+        sample_ids (stochastic depth only): the number under which image i draws its masks, default i - its position in this input."""
         plan = None
         if isinstance(images, (list, tuple)):
             if not images or any(not torch.is_tensor(t) or t.dim() != 3 for t in images):
@@ -423,9 +504,19 @@ class ConvNextTower(Tower):
                 raise ValueError(f"ConvNeXt needs at least 32x32 pixels, got {tuple(images.shape)}")
             device = images.device
         anchor = self._record_forward(device)
+        seed = None
+        if self.stochastic_depth_active():      # one seed per forward; a checkpointed recomputation reuses the schedules made from it
+            if self.next_drop_seed is not None:
+                seed, self.next_drop_seed = int(self.next_drop_seed), None
+            else:
+                seed = self._drop_seeds.draw()
+            ids = list(range(len(images))) if sample_ids is None else [int(i) for i in sample_ids]
+            if len(ids) != len(images):
+                raise ValueError(f"sample_ids names {len(ids)} images, the input holds {len(images)}")
+            seed = (seed, ids)
         if plan is None:
-            return _ConvNextFn.apply(self, images.float().contiguous(), anchor, None)
-        return _ConvNextFn.apply(self, [t.float() for t in images], anchor, plan)
+            return _ConvNextFn.apply(self, images.float().contiguous(), anchor, None, seed)
+        return _ConvNextFn.apply(self, [t.float() for t in images], anchor, plan, seed)
 
 
 def group_by_size(sizes, micro_batch):
@@ -447,17 +538,20 @@ def group_by_size(sizes, micro_batch):
 
 class _ConvNextFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tower, images, anchor, plan):
+    def forward(ctx, tower, images, anchor, plan, sd_seed=None):
+        """sd_seed: None, or (seed, sample ids) of a forward that applies stochastic depth."""
         tower._refresh_working_copies()
         save = anchor is not None
         mb = tower.micro_batch
         ckpt = save and tower.checkpoint
         if plan is None:
             count, device = images.shape[0], images.device
+            mbs = [list(range(i, min(i + mb, count))) for i in range(0, count, mb)]
             parts = [(lambda i=i: images[i:i + mb]) for i in range(0, count, mb)]
             alive = [(min(mb, count) if ckpt else count, images.shape[-2], images.shape[-1])]
         else:                               # images of several sizes: one [k, Cin, H, W] tensor per group-micro-batch, built when it is needed
             count, device = len(images), images[0].device
+            mbs = plan[0]
             parts = [(lambda idx=idx: torch.stack([images[j] for j in idx]).contiguous()) for idx in plan[0]]
             by_size = {}
             for idx in plan[0]:
@@ -474,12 +568,24 @@ class _ConvNextFn(torch.autograd.Function):
         if save:
             dec = tower._decide_saves(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
             tower.save_ln, tower.save_gelu, tower.fp8_bwd_now = dec         # (the latest forward's, for whoever reports them: bench.py)
-        out, parts = forward_parts(parts, lambda pix, saving: tower._forward_mb(pix, blocks, dec if saving else None), ckpt)
+        inverse = plan[1] if plan is not None else list(range(count))
+        if sd_seed is not None:
+            # stochastic depth: the mask of a sample is a function of (seed, block, its index in the INPUT); every micro-batch gets its
+            # schedule here, once, and carries it along with its pixels (a part is opaque to forward_parts / backward_parts), so the
+            # recomputation of a checkpointed part executes the same record
+            rates = SD.block_rates(tower.stochastic_depth_prob, tower.depths)
+            scheds = [SD.schedule(SD.keep_matrix(sd_seed[0], [sd_seed[1][i] for i in idx], rates)) for idx in mbs]
+            parts = [(lambda part=part, sch=sch: (part(), sch)) for part, sch in zip(parts, scheds)]
+            inverse = SD.processing_order(mbs, scheds)[1]
+            run = lambda x, saving: tower._forward_mb(x[0], blocks, dec if saving else None, x[1])      # noqa: E731
+        else:
+            run = lambda pix, saving: tower._forward_mb(pix, blocks, dec if saving else None)           # noqa: E731
+        out, parts = forward_parts(parts, run, ckpt)
         ctx.tower, ctx.parts = tower, parts if save else None
         ctx.plan, ctx.decision = blocks, dec
-        ctx.inverse = None
-        if plan is not None and plan[1] != list(range(count)):
-            ctx.inverse = torch.tensor(plan[1], device=device)
+        ctx.inverse, ctx.sd = None, sd_seed is not None
+        if inverse != list(range(count)):
+            ctx.inverse = torch.tensor(inverse, device=device)
             out = out.index_select(0, ctx.inverse)             # processing order -> input order
         return out
 
@@ -494,6 +600,8 @@ class _ConvNextFn(torch.autograd.Function):
 
         def bwd(d, saved, final):            # final: the GEMM-shaped temporaries are folded, and (the step's last backward) announced
             tower._backward_mb(d, saved, tmp, final=final, announce=final and last_backward(tower))
-        backward_parts(ctx.parts, dfeat, lambda pix: tower._forward_mb(pix, ctx.plan, ctx.decision)[1], bwd)
+        again = (lambda x: tower._forward_mb(x[0], ctx.plan, ctx.decision, x[1])[1]) if ctx.sd else \
+            (lambda pix: tower._forward_mb(pix, ctx.plan, ctx.decision)[1])
+        backward_parts(ctx.parts, dfeat, again, bwd)
         backward_finished(tower)
-        return None, None, None, None
+        return None, None, None, None, None

@@ -88,9 +88,9 @@ class _ConvNextEncoder(ConvNextTower):
     VARIANT = "tiny"
 
     def __init__(self, pretrained=None, image_features_dimension=None, in_chans=1, scale16=True, micro_batch=64, freeze=False,
-                 checkpoint=False, fp8=False):
+                 checkpoint=False, fp8=False, stochastic_depth_prob=0.0):
         super().__init__(self.VARIANT, in_chans=in_chans, scale16=scale16, micro_batch=micro_batch, checkpoint=checkpoint,
-                         fp8=fp8)
+                         fp8=fp8, stochastic_depth_prob=stochastic_depth_prob)
         if isinstance(pretrained, str) and os.path.isfile(pretrained):
             sd = _load_state_file(pretrained)
             sd = {k[len("model."):] if k.startswith("model.") else k: v for k, v in sd.items()}

@@ -59,7 +59,7 @@ class MMGCLIP(nn.Module):
                 freeze=_get(ie, "freeze", False),
                 checkpoint=_get(ie, "checkpoint", False),
                 **({"image_size": _get(ie, "image_size", 224)} if enc_name == "ViTB16Encoder" else
-                   {"fp8": _get(ie, "fp8", False)})).to(self.device)
+                   {"fp8": _get(ie, "fp8", False), "stochastic_depth_prob": _get(ie, "stochastic_depth_prob", 0.0)})).to(self.device)
             logger.info(f"Using {self.image_encoder.__class__.__name__}")
 
         te = self.config.networks.text_encoder
