@@ -215,6 +215,16 @@ int mmg_grad_clip_finalize(const double* partials, int n, float max_norm, float*
 int mmg_adamw_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int step, const float* clip, const int* skipped,
                            mmg_stream_t stream);
+/* mmg_adamw_step / mmg_adamw_step_guarded over an arena whose parameters sit in several torch param groups, in one launch
+ * (csrc/adamw_groups.hip).  The reference hands torch.optim.AdamW ONE group (ClassifierExperiment.py:74); param groups are torch's own
+ * means for no-decay sets and layer-wise learning rates (additive, mmg_abi_version() stays 5).  chunk_group (device, n / 64 bytes):
+ * the group of elements [64 c, 64 c + 64) - params.ParamArena starts every parameter on a 64-element boundary; a chunk whose byte
+ * is >= n_groups is left untouched.  group_lr / group_wd are HOST arrays of n_groups floats, read during the call and passed to the
+ * kernel by value: they may change at every step.  n a multiple of 64, 1 <= n_groups <= 128, p / g / m / v 16-byte aligned.
+ * clip == NULL (then skipped must be NULL): mmg_adamw_step's arithmetic with grad_scale 1; clip given: mmg_adamw_step_guarded's. */
+int mmg_adamw_step_groups(float* p, const float* g, float* m, float* v, long long n, const unsigned char* chunk_group, int n_groups,
+                          const float* group_lr, const float* group_wd, float beta1, float beta2, float eps, int step,
+                          const float* clip, const int* skipped, mmg_stream_t stream);
 
 /* ConvNeXt layer scale (out = x + gamma * (G W2^T + b2)): converts the unscaled weight-gradient GEMM results
  * dW2raw [C,K], db2raw [C] into dgamma, dW2, db2 (all ACCUMULATED).  torchvision CNBlock.layer_scale. */

@@ -8,7 +8,9 @@ shape prompts, 8 BI-RADS prompts; prompt embeddings cached once per call instead
 `test()` (the offline Evaluator with bootstrap CIs, confusion matrices and plots) is out of scope.
 Additive options: `distributed.global_loss`, `optimizer.config.fused` (FusedAdamW over the parameter arenas),
 `optimizer.config.max_grad_norm` / `optimizer.config.skip_nonfinite` (clip the gradients by their global norm and do not step on a
-NaN / Inf gradient; the reference goes from backward straight to step, :115-118, and so does a shipped config).
+NaN / Inf gradient; the reference goes from backward straight to step, :115-118, and so does a shipped config),
+`optimizer.config.layer_decay` / `no_decay_1d` / `image_lr_mult` / `text_lr_mult` (param groups, optim_groups.py; absent from the
+shipped configs, and then AdamW gets `model.parameters()` as its one group, :74).
 """
 import os
 import time
@@ -83,16 +85,26 @@ class ClassifierExperiment:
             skip = skip and "optimizer.config.skip_nonfinite" in overridden_keys(config)
         self.skip_nonfinite = skip
         self.skipped_steps, self._last_grad_norm = 0, None                # (the torch.optim.AdamW path counts on the host)
+        # param groups (additive: no-decay set, layer-wise lr decay, per-tower lr; optim_groups.py), built once and handed to BOTH
+        # optimizers.  A config composed as shipped has none of the four keys: one group, `model.parameters()` itself, as before
+        from ..optim_groups import build_param_groups, group_table
+        decay = _get(config, "optimizer.config.layer_decay", None)
+        mults = [_get(config, f"optimizer.config.{k}_lr_mult", 1.0) for k in ("image", "text")]
+        groups = build_param_groups(self.model, lr, wd, layer_decay=decay, no_decay_1d=bool(_get(config, "optimizer.config.no_decay_1d", False)),
+                                    image_lr_mult=1.0 if mults[0] is None else mults[0], text_lr_mult=1.0 if mults[1] is None else mults[1])
+        if comm is None or comm.rank == 0:
+            logger.info(f"Optimizer param groups:\n{group_table(groups)}")
+        params = groups if len(groups) > 1 else groups[0]["params"]       # (one group: no 'name' key in the checkpoint's param_groups)
         if _get(config, "optimizer.config.fused", False):
             # the towers' parameter arenas do not exist yet (they are built at the first forward): FusedAdamW finds them from
             # the parameters at every step.  EVERY parameter is listed, frozen ones included, exactly as the reference hands
             # `model.parameters()` to torch.optim.AdamW (ClassifierExperiment.py:74): the param-group layout of a checkpoint's
             # optimizer_state_dict is then the same in both directions (frozen parameters never get a gradient and are skipped)
             from ..optim import FusedAdamW
-            self.optimizer = FusedAdamW(self.model.parameters(), lr=lr, weight_decay=wd, max_grad_norm=self.max_grad_norm,
+            self.optimizer = FusedAdamW(params, lr=lr, weight_decay=wd, max_grad_norm=self.max_grad_norm,
                                         skip_nonfinite=self.skip_nonfinite)
         else:
-            self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=lr, weight_decay=wd)
+            self.optimizer = torch.optim.AdamW(params, lr=lr, weight_decay=wd)
 
         if self.config.scheduler.name == "cosine":
             self.scheduler = LinearWarmupCosineAnnealingLR(self.optimizer, total_steps=self.config.scheduler.config.epochs,

@@ -264,6 +264,25 @@ def adamw_step_guarded(p, g, m, v, p16, lr, beta1, beta2, eps, wd, step, clip, s
          float(eps), float(wd), int(step), ptr(clip), ptr(skipped), stream())
 
 
+ADAMW_MAX_GROUPS = 128      # csrc/adamw_groups.hip: AG_MAX_GROUPS
+
+
+def adamw_step_groups(p, g, m, v, chunk_group, group_lr, group_wd, beta1, beta2, eps, step, clip=None, skipped=None):
+    """One AdamW launch over a flat arena in several param groups: chunk_group (uint8 [p.numel() / 64], device) names the group of every
+    64-element chunk, group_lr / group_wd are host sequences (passed by value: they may differ at every step).  clip / skipped as in
+    adamw_step_guarded; both None = adamw_step's arithmetic."""
+    n_groups = len(group_lr)
+    assert len(group_wd) == n_groups and chunk_group.dtype == torch.uint8 and chunk_group.is_contiguous()
+    assert chunk_group.numel() * 64 == p.numel() == g.numel() == m.numel() == v.numel()
+    assert clip is None or (clip.dtype == torch.float32 and clip.numel() >= 3)
+    assert skipped is None or skipped.dtype == torch.int32
+    _hip.require_gpu(p, g, m, v, chunk_group, clip, skipped)
+    lrs = (ctypes.c_float * max(n_groups, 1))(*[float(x) for x in group_lr])
+    wds = (ctypes.c_float * max(n_groups, 1))(*[float(x) for x in group_wd])
+    call("mmg_adamw_step_groups", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(chunk_group), n_groups, lrs, wds, float(beta1),
+         float(beta2), float(eps), int(step), ptr(clip), ptr(skipped), stream())
+
+
 def dwconv_mfma_pays(n, H, W, C, flip):
     """Where the matrix-core kernel beats the VALU one in the same-process A/B (tools/dwm_scale.py at n = 256, tools/dwm_scale_b.py at n = 64;
     profiles/r04_dwconv_mfma_scale2.txt, _scale_b2.txt - after the kernel's loads were made unconditional and its spills removed: -25 % / -23 % at

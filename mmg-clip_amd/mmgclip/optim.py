@@ -9,6 +9,13 @@ The one-launch path is taken when every parameter of an arena is trainable, in t
 arena's flat gradient buffer; otherwise its trainable parameters are updated one by one and the arena is told so
 (`touch()`), which is what makes the towers rebuild their bf16 working copies.
 
+Param groups (no-decay sets, layer-wise learning rates: optim_groups.build_param_groups): an arena is considered once per step, across
+all groups.  Sitting in one group it takes the launch above, symbol for symbol; spread over several groups that share `betas` and `eps`
+it still goes out as ONE launch (csrc/adamw_groups.hip: mmg_adamw_step_groups), with a cached one-byte-per-64-elements map from chunk
+to group on the device and the groups' `lr` / `weight_decay` read from `param_groups` at every step and passed by value.  Mixed
+`betas` / `eps`, more than 128 distinct (lr, weight_decay) pairs, a partly frozen arena and loose tensors take the per-tensor path,
+each tensor with its own group's values.
+
 State layout = torch.optim.AdamW's: `state[p] = {'step': fp32 0-d tensor, 'exp_avg', 'exp_avg_sq'}`, so
 `state_dict()` / `load_state_dict()` (what EarlyStopper writes as 'optimizer_state_dict', callbacks/early_stopping.py:52-65)
 round-trip and are interchangeable with the reference's torch.optim.AdamW PROVIDED both list the same parameters in the same order:
@@ -32,6 +39,19 @@ import math
 import torch
 
 from . import kernels as K
+
+
+def build_chunk_map(arena, slots):
+    """uint8 [arena.size / 64] on the host: the slot (`slots[i]` of the i-th arena parameter) of every 64-element chunk.  ParamArena starts
+    each parameter on a 64-element boundary, so a chunk belongs to exactly one parameter; the padding behind a parameter is part of its
+    last chunk (zero in the gradient and the moments, so it stays zero whatever the slot's hyper-parameters are)."""
+    assert arena.size % 64 == 0 and len(slots) == len(arena.params)
+    out = torch.empty(arena.size // 64, dtype=torch.uint8)
+    for n, p, s in zip(arena.names, arena.params, slots):
+        assert 0 <= s < 256 and arena.offsets[n] % 64 == 0
+        first = arena.offsets[n] // 64
+        out[first:first + (p.numel() + 63) // 64] = s
+    return out
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -117,28 +137,60 @@ class FusedAdamW(torch.optim.Optimizer):
         return st
 
     # ---- the step --------------------------------------------------------------------------------------------------
+    def _grouped_launch(self, arena, group_of):
+        """A whole arena whose parameters sit in several param groups -> (device chunk map, [lr per slot], [weight_decay per slot]) for
+        ONE mmg_adamw_step_groups launch, or None when the launch cannot express it (the groups differ in betas / eps, or span more
+        than 128 distinct (lr, weight_decay) pairs).  A slot is a param group; only beyond 128 groups are groups of equal (lr,
+        weight_decay) merged.  lr / weight_decay are read here, at every step; the map is cached on the arena's flat state and rebuilt
+        when the arena was rebuilt (new flat state) or a parameter's slot changed."""
+        owners = [group_of[id(p)] for p in arena.params]
+        used = sorted(set(owners))
+        groups = [self.param_groups[gi] for gi in used]
+        if any(tuple(g["betas"]) != tuple(groups[0]["betas"]) or g["eps"] != groups[0]["eps"] for g in groups[1:]):
+            return None
+        pairs = [(float(g["lr"]), float(g["weight_decay"])) for g in groups]
+        if len(used) <= K.ADAMW_MAX_GROUPS:
+            slot_of = {gi: s for s, gi in enumerate(used)}
+        else:
+            distinct = list(dict.fromkeys(pairs))
+            if len(distinct) > K.ADAMW_MAX_GROUPS:
+                return None
+            slot_of = {gi: distinct.index(pair) for gi, pair in zip(used, pairs)}
+            pairs = distinct
+        slots = tuple(slot_of[gi] for gi in owners)
+        fs = self._flat_state(arena)
+        if fs.get("slots") != slots:
+            fs["slots"], fs["chunk_map"] = slots, build_chunk_map(arena, slots).to(arena.data.device)
+        return fs["chunk_map"], [lr for lr, _ in pairs], [wd for _, wd in pairs]
+
     def _collect(self):
-        """Every update this step will make, each gradient exactly once: [(p, g, m, v, (lr, b1, b2, eps, wd), step)] - a whole arena
-        as ONE flat entry (its 64-element padding gaps are zero in the gradient and stay zero), anything else per tensor - and the
+        """Every update this step will make, each gradient exactly once: [(p, g, m, v, (lr, b1, b2, eps, wd), step, grouped)] - a whole
+        arena as ONE flat entry (its 64-element padding gaps are zero in the gradient and stay zero; `grouped` = `_grouped_launch`'s
+        result when it sits in several groups, whose lr / wd then replace the entry's own), anything else per tensor - and the
         arenas that must be told their parameters moved.  Advances the host step counters; launches nothing but state set-up."""
-        jobs, touched = [], {}
+        jobs, touched, done = [], {}, set()
+        group_of = {id(p): gi for gi, group in enumerate(self.param_groups) for p in group["params"]}
         for group in self.param_groups:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             hyper = (lr, b1, b2, eps, wd)
-            in_group = {id(p) for p in group["params"]}
-            arenas, done = {}, set()
+            arenas = {}
             for p in group["params"]:
                 a = getattr(p, "_mmg_arena", None)
-                if a is not None and a.is_bound():
+                if a is not None and a.is_bound() and id(p) not in done:
                     arenas[id(a)] = a
-            for arena in arenas.values():
-                whole = all(p.requires_grad and id(p) in in_group and p.grad is not None and
+            for arena in arenas.values():        # an arena is considered once per step, at the first group that lists one of its parameters
+                whole = all(p.requires_grad and id(p) in group_of and p.grad is not None and
                             p.grad.data_ptr() == arena.g(n).data_ptr() for n, p in zip(arena.names, arena.params))
                 if not whole:
                     continue
+                grouped = None
+                if len({group_of[id(p)] for p in arena.params}) > 1:
+                    grouped = self._grouped_launch(arena, group_of)
+                    if grouped is None:          # mixed betas / eps, or too many groups: per tensor, each with its own group's values
+                        continue
                 fs = self._flat_state(arena)
                 fs["step"] += 1
-                jobs.append((arena.data, arena.grad, fs["m"], fs["v"], hyper, int(fs["step"])))
+                jobs.append((arena.data, arena.grad, fs["m"], fs["v"], hyper, int(fs["step"]), grouped))
                 touched[id(arena)] = arena
                 done.update(id(p) for p in arena.params)
             for p in group["params"]:
@@ -150,7 +202,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if st["step"].data_ptr() in {fs["step"].data_ptr() for fs in self._flat.values()}:
                     st["step"] = st["step"].clone()              # leaving the whole-arena path: own counter from here on
                 st["step"] += 1
-                jobs.append((p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], hyper, int(st["step"])))
+                jobs.append((p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], hyper, int(st["step"]), None))
                 a = getattr(p, "_mmg_arena", None)
                 if a is not None:                # the update goes through a raw pointer: p._version does not move, say so
                     touched[id(a)] = a
@@ -184,10 +236,15 @@ class FusedAdamW(torch.optim.Optimizer):
         if guarded and jobs:
             # no .item(), no .cpu(), no synchronisation: the coefficient, the go/no-go and Adam's clock are read by the AdamW launches
             clip, skipped = self._clip_state([j[1] for j in jobs])
-            for p, g, m, v, hyper, t in jobs:
-                K.adamw_step_guarded(p, g, m, v, None, *hyper, t, clip, skipped)
         else:
-            for p, g, m, v, hyper, t in jobs:
+            clip = skipped = None
+        for p, g, m, v, hyper, t, grouped in jobs:
+            if grouped is not None:              # a whole arena in several groups: one launch, lr / weight_decay per 64-element chunk
+                chunk_map, lrs, wds = grouped
+                K.adamw_step_groups(p, g, m, v, chunk_map, lrs, wds, hyper[1], hyper[2], hyper[3], t, clip, skipped)
+            elif clip is not None:
+                K.adamw_step_guarded(p, g, m, v, None, *hyper, t, clip, skipped)
+            else:
                 K.adamw_step(p, g, m, v, None, *hyper, t)
         for a in touched:        # (on a skipped step too: harmless, the towers re-cast unchanged parameters)
             a.touch()
