@@ -264,7 +264,7 @@ int mmg_dwconv7_nhwc(const void* x, const float* w, const float* bias, const voi
                      int C, int flip, mmg_stream_t stream);
 /* The same contract on the matrix cores (ABI 5, csrc/dwconv7_mfma.hip): per channel and kernel row the 1-D convolution along x is a product with a
  * banded Toeplitz matrix (v_mfma_f32_16x16x32_bf16, taps rounded to bf16, fp32 accumulation); the NHWC <-> channel-plane layout changes run on the
- * LDS transposed reads.  With `add` the sum is rounded to bf16 twice (convolution, then + add).  (Rounds 1 - 2 had an earlier kernel of this name,
+ * LDS transposed reads.  With `add` the fp32 sum is rounded to bf16 once, as in mmg_dwconv7_nhwc (it was rounded twice - convolution, then + add - until tests/test_dwconv_gpu.py held both kernels to one bar).  (Rounds 1 - 2 had an earlier kernel of this name,
  * at parity with the VALU one and removed in ABI 4.) */
 int mmg_dwconv7_nhwc_mfma(const void* x, const float* w, const float* bias, const void* add, void* y, int n, int H, int W,
                           int C, int flip, mmg_stream_t stream);

@@ -17,7 +17,8 @@
 //         [32][22 rows][48 x] (96-byte rows: conflict-free ds_read_b128 of the data operand: lane = row, 8 consecutive x)
 //   out:  swapped MFMA (lane = row, 4 consecutive x_out) --ds_write_b64--> planes [32][16][16] --ds_read_b64_tr_b16 (4 channels x
 //         16 x: lane = pixel, 4 consecutive channels) x 2--> ds_write_b128 --> NHWC tile --ds_read_b128--> 16-byte global stores
-//         (+ the residual-gradient add of the data-gradient call)
+//         (+ the residual-gradient add of the data-gradient call: the ADD instantiations send the fp32 accumulators through these
+//         transposes as two 16-bit halves, so that the sum is rounded to bf16 once - see DM_LO_PLANE)
 // One 16-wave (or 8-wave) workgroup per CU, persistent over the (image, tile) items of ONE 32-channel slab; a wave owns 2 (4) channels and
 // keeps their 14 (28) Toeplitz fragments (56 / 112 registers) for its whole life.  The halo tile of item k + 2 is in flight in registers
 // while item k is computed (see "Memory pipeline" below).  Pitches (tools: bank model of MI355X_MICROARCH.md, LDS section): plane rows 96 B (b128 reads conflict-free under
@@ -42,7 +43,15 @@
 #define DM_OFF_PLANAR DM_IN_BYTES
 #define DM_OFF_OUT (DM_OFF_PLANAR + DM_PLANAR)
 #define DM_LDS (DM_OFF_OUT + DM_OUT_BYTES)
-static_assert(DM_LDS <= 160 * 1024, "LDS budget");
+// ADD instantiations carry the fp32 accumulators to the output pass WHOLE, as two 16-bit halves through the same 16-bit transposes: the high
+// halves take the path of the bf16 outputs, the low halves go D -> the (consumed) NHWC input tile region, planes DM_LO_PLANE apart (= DM_PLANE
+// mod 256: the bank pattern of the high halves) -> E -> a second NHWC output tile.  F rebuilds the fp32 value, adds the residual operand and
+// rounds ONCE, as the VALU kernels do (rounding conv + bias to bf16 first and the sum again was off by up to half an ulp of the LARGER of the two).
+#define DM_LO_PLANE 848
+#define DM_OFF_OUT_LO (DM_OFF_OUT + DM_OUT_BYTES)
+#define DM_LDS_ADD (DM_OFF_OUT_LO + DM_OUT_BYTES)
+static_assert(DM_LDS_ADD <= 160 * 1024, "LDS budget");
+static_assert(DM_LO_PLANE >= DM_T * DM_OROWB && DM_CB * DM_LO_PLANE <= DM_IN_BYTES && DM_LO_PLANE % 16 == 0, "the low halves fit the input tile region");
 static_assert(DM_PLANE % 16 == 0 && DM_T * DM_OROWB <= DM_PLANE, "alignment / the output rows fit the plane they replace");
 
 struct DwM {
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void dwconv7_mfma_kernel(const DwM
     };
 
     // ---- zero what is read but never written: the plane columns 24 .. 47 ------------------------------------------------------------------
-    for (int i = tid; i < (DM_LDS - DM_OFF_PLANAR) / 16; i += DM_THREADS) *reinterpret_cast<uint4*>(smem + DM_OFF_PLANAR + i * 16) = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < ((ADD ? DM_LDS_ADD : DM_LDS) - DM_OFF_PLANAR) / 16; i += DM_THREADS) *reinterpret_cast<uint4*>(smem + DM_OFF_PLANAR + i * 16) = make_uint4(0, 0, 0, 0);
 
     // ---- Toeplitz fragments of this wave's 4 channels: element j of lane (n = li, k group lg) = T_ky[k = 8 lg + j][n] ------------------------
     // (the slab's 49 x 32 taps go through LDS once - coalesced loads, then branch-free selects; the region is the plane area zeroed above)
@@ -315,8 +324,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void dwconv7_mfma_kernel(const DwM
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (ADD) {                        // both halves of the fp32 bits (the input tile region is free since the barrier behind B)
+                    char* lo0 = smem + DM_OFF_IN + (CPW * wave + 2 * cp) * DM_LO_PLANE;
+                    auto hi2 = [](float a, float b) { return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u); };
+                    auto lo2 = [](float a, float b) { return (__float_as_uint(a) & 0xffffu) | (__float_as_uint(b) << 16); };
+                    *reinterpret_cast<uint2*>(pl0 + d_wr) = make_uint2(hi2(acc0[0], acc0[1]), hi2(acc0[2], acc0[3]));
+                    *reinterpret_cast<uint2*>(lo0 + d_wr) = make_uint2(lo2(acc0[0], acc0[1]), lo2(acc0[2], acc0[3]));
+                    __builtin_amdgcn_sched_barrier(0);      // (one channel's four words at a time)
+                    *reinterpret_cast<uint2*>(pl0 + DM_PLANE + d_wr) = make_uint2(hi2(acc1[0], acc1[1]), hi2(acc1[2], acc1[3]));
+                    *reinterpret_cast<uint2*>(lo0 + DM_LO_PLANE + d_wr) = make_uint2(lo2(acc1[0], acc1[1]), lo2(acc1[2], acc1[3]));
+                } else {
                 *reinterpret_cast<uint2*>(pl0 + d_wr) = make_uint2(pack2bf(acc0[0], acc0[1]), pack2bf(acc0[2], acc0[3]));
                 *reinterpret_cast<uint2*>(pl0 + DM_PLANE + d_wr) = make_uint2(pack2bf(acc1[0], acc1[1]), pack2bf(acc1[2], acc1[3]));
+                }
                 __builtin_amdgcn_sched_barrier(0);          // (two channels' fragments in flight at a time: 112 registers hold T)
             }
         }
@@ -327,6 +347,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void dwconv7_mfma_kernel(const DwM
             for (int it = 0; it < ER; ++it) {
                 const bf16x4 lo = dm_tr(e_src + it * DM_OROWB), hi = dm_tr(e_src + it * DM_OROWB + 4 * DM_PLANE);
                 *reinterpret_cast<bf16x8*>(e_dst + it * (DM_T * DM_OPIX)) = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                if constexpr (ADD) {                        // the low halves of the accumulators: same transposes, second output tile
+                    // (its lane address is re-derived from the hardware lane id here: kept in a register of its own across the item loop it was
+                    //  one more spilled register, reloaded behind `s_waitcnt vmcnt(0)` - a drain of the halo prefetch per item)
+                    const int fl = fresh_tid() & 63, fq = fl & 15;
+                    const char* e_src_lo = smem + DM_OFF_IN + (8 * (fl >> 4) + (fq >> 2)) * DM_LO_PLANE + (ER * wave) * DM_OROWB + (fq & 3) * 8;
+                    const bf16x4 l0 = dm_tr(e_src_lo + it * DM_OROWB), l1 = dm_tr(e_src_lo + it * DM_OROWB + 4 * DM_LO_PLANE);
+                    *reinterpret_cast<bf16x8*>(e_dst + DM_OUT_BYTES + it * (DM_T * DM_OPIX)) = bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                }
             }
         }
         dm_barrier();
@@ -340,10 +368,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void dwconv7_mfma_kernel(const DwM
                     uint4 v = *reinterpret_cast<const uint4*>(f_src + it * ((DM_THREADS / 4) * DM_OPIX));
                     if constexpr (ADD) {
                         const uint4 a = addv[it];
-                        v.x = pack2bf(bf2f_lo(v.x) + bf2f_lo(a.x), bf2f_hi(v.x) + bf2f_hi(a.x));
-                        v.y = pack2bf(bf2f_lo(v.y) + bf2f_lo(a.y), bf2f_hi(v.y) + bf2f_hi(a.y));
-                        v.z = pack2bf(bf2f_lo(v.z) + bf2f_lo(a.z), bf2f_hi(v.z) + bf2f_hi(a.z));
-                        v.w = pack2bf(bf2f_lo(v.w) + bf2f_lo(a.w), bf2f_hi(v.w) + bf2f_hi(a.w));
+                        const uint4 l = *reinterpret_cast<const uint4*>(f_src + DM_OUT_BYTES + it * ((DM_THREADS / 4) * DM_OPIX));
+                        // fp32 accumulator = high half (v) | low half (l); + the operand in fp32; ONE rounding to bf16
+                        auto sum2 = [](unsigned h, unsigned lw, unsigned ad) {
+                            return pack2bf(__uint_as_float((h << 16) | (lw & 0xffffu)) + bf2f_lo(ad),
+                                           __uint_as_float((h & 0xffff0000u) | (lw >> 16)) + bf2f_hi(ad));
+                        };
+                        v.x = sum2(v.x, l.x, a.x);
+                        v.y = sum2(v.y, l.y, a.y);
+                        v.z = sum2(v.z, l.z, a.z);
+                        v.w = sum2(v.w, l.w, a.w);
                     }
                     store16_stream(p.y + tile_el + o_off[it], v, p.nt);
                 }
@@ -380,8 +414,8 @@ MMG_API int mmg_dwconv7_nhwc_mfma(const void* x, const float* w, const float* bi
     MMG_NOTE_KERNEL("dwconv7_mfma_kernel<%s, %d>", flip ? "true" : "false", nw == 8 ? 8 : 16);
 #define DM_LAUNCH(FL, W_, AD)                                                                                 \
     do {                                                                                                      \
-        mmg_allow_lds(dwconv7_mfma_kernel<FL, W_, AD>, DM_LDS);                                               \
-        hipLaunchKernelGGL((dwconv7_mfma_kernel<FL, W_, AD>), dim3(grid), dim3(W_ * 64), DM_LDS, stream, p);  \
+        mmg_allow_lds(dwconv7_mfma_kernel<FL, W_, AD>, AD ? DM_LDS_ADD : DM_LDS);                             \
+        hipLaunchKernelGGL((dwconv7_mfma_kernel<FL, W_, AD>), dim3(grid), dim3(W_ * 64), AD ? DM_LDS_ADD : DM_LDS, stream, p);  \
     } while (0)
 #define DM_LAUNCH_W(FL, AD) do { if (nw == 8) DM_LAUNCH(FL, 8, AD); else DM_LAUNCH(FL, 16, AD); } while (0)
     if (flip) { if (add) DM_LAUNCH_W(true, true); else DM_LAUNCH_W(true, false); }
