@@ -715,12 +715,17 @@ MMG_API int mmg_cnblock_bwdw(const void* dy, const void* xd, const float* ln_w, 
     const int grid = a.ntiles < cap ? a.ntiles : cap;
     // launch 1 with 12 waves (three per SIMD, 168 registers): same-box A/B at 16.8 M rows, two runs each: 13.10 / 13.15 ms against
     // 12.94 / 13.09 with 8 waves - the launch is bound by VALU issue (GELU), not by latency, so the third wave buys nothing.  Off.
-    static const int w12 = getenv("MMG_BWDW_W12") ? atoi(getenv("MMG_BWDW_W12")) : 0;
+    // (MMG_BWDW_W12: read per call like the other knobs here, so that a test reaches <96, 1, 12, 0> in the process that ran the default)
+    const char* ew = getenv("MMG_BWDW_W12");
+    const int w12 = ew ? atoi(ew) : 0;
     // schedule of launch 1 (see the kernel's VAR comment); MMG_BWDW_VAR = 0 / 1 / 2 for same-process A/B runs (tools/bwdw_bench.py)
     const char* ev = getenv("MMG_BWDW_VAR");
     const int var = ev ? atoi(ev) : BW_DEFAULT_VAR;
+    const char* eh = getenv("MMG_BWDW_HTO");                 // (read per call: same-process A/B runs, tools/bwdw_bench.py)
+    const int hto = eh ? atoi(eh) : BW_DEFAULT_HTO;
     typedef BwCfg<96> Cfg;
-    MMG_NOTE_KERNEL("cnblock_bwdw_kernel<96, *>");
+    // both launches by name, as the branches below choose them
+    MMG_NOTE_KERNEL("cnblock_bwdw_kernel<96, 1, %d, %d> + <96, 2, 8, %d>", w12 ? 12 : 8, w12 ? 0 : (var == 2 ? 2 : (var == 1 ? 1 : 0)), hto ? 1 : 0);
     if (w12) {
         mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 12, 0>, Cfg::LDS);
         hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 12, 0>), dim3(grid), dim3(768), Cfg::LDS, stream, a);
@@ -734,8 +739,6 @@ MMG_API int mmg_cnblock_bwdw(const void* dy, const void* xd, const float* ln_w, 
         mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 8, 0>, Cfg::LDS);
         hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 8, 0>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
     }
-    const char* eh = getenv("MMG_BWDW_HTO");                 // (read per call: same-process A/B runs, tools/bwdw_bench.py)
-    const int hto = eh ? atoi(eh) : BW_DEFAULT_HTO;
     if (hto) {
         mmg_allow_lds(cnblock_bwdw_kernel<96, 2, 8, 1>, Cfg::LDS);
         hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 2, 8, 1>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
