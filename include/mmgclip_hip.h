@@ -337,6 +337,34 @@ int mmg_cluster_mean_cols_fwd(const float* logits, int ld, int n, int N, const l
 int mmg_cluster_mean_cols_bwd(const float* dout, int ldo, int n, int N, const long long* labels, const int* counts,
                               float* dlogits, int ld, mmg_stream_t stream);
 
+/* The same loss from the (gathered) L2-normalised embeddings, no [n,N] logits (mmgclip/loss/losses.py:164-216).  By linearity the
+ * column-averaged logits are s <I_i, Tbar_c> with Tbar_c the mean text embedding of cluster c, so both cross-entropies are
+ * "rows of X [n_loc,D] against Y [M,D] with an int64 label per row" (image side: Y = Tbar, M = k; text side: Y = I, M = N).
+ * D % 32 == 0, 32 <= D <= 1024; n_loc, M > 0.
+ *
+ * mmg_clip_labelled_rows_fwd:  lse[r] = logsumexp_m( s <X_r,Y_m> ),  pos[r] = s <X_r, Y_{row_label[r]}>  (losses.py:164-216;
+ *   a label outside [0,M) matches no column: pos = 0). */
+int mmg_clip_labelled_rows_fwd(const float* X, const float* Y, const float* scale, const long long* row_label, int n_loc, int M,
+                               int D, float* lse, float* pos, mmg_stream_t stream);
+/* Gradient products dX[r,:] (+)= s * sum_m g[r,m] Y[m,:]  (accumulate != 0 adds into dX), z = s <X_r,Y_m>, gout a device scalar
+ * (NULL = 1), coef = 1/(2 N_global); autograd of losses.py:164-216 through the two logit products:
+ *   _row:  g[r,m] = coef gout ( exp(z - lse_row[r]) - [m == row_label[r]] );  dscale += sum g[r,m] <X_r,Y_m>  (dscale may be NULL)
+ *   _col:  g[r,m] = coef gout w[r] ( exp(z - lse_col[m]) - [col_label[m] == key[r]] ),  lse_col / col_label: [M] (the transposed
+ *          problem's row log-sum-exps and labels),  key[r] = row_key ? row_key[r] : key_off + r,
+ *          w[r] = counts ? 1 / counts[key[r]] : 1  (counts int32 [n_counts]; needs row_key).  No dscale: each softmax element is
+ *          counted once, by its _row product. */
+int mmg_clip_labelled_rows_bwd_row(const float* X, const float* Y, const float* scale, const float* lse_row,
+                                   const long long* row_label, const float* gout, float coef, int n_loc, int M, int D,
+                                   int accumulate, float* dX, float* dscale, mmg_stream_t stream);
+int mmg_clip_labelled_rows_bwd_col(const float* X, const float* Y, const float* scale, const float* lse_col,
+                                   const long long* col_label, const long long* row_key, int key_off, const int* counts,
+                                   int n_counts, const float* gout, float coef, int n_loc, int M, int D, int accumulate,
+                                   float* dX, mmg_stream_t stream);
+/* Cluster centroids (the column average of losses.py:164-186 moved onto the embeddings): out[c,:] = mean_{j: labels[j]==c} T[j,:],
+ * T fp32 [N,D], out fp32 [k,D].  Members are added in ascending j by one wave per cluster, no float atomics: the same bits in give
+ * the same bits out on every rank and in every run.  N <= 16384, 1 <= k <= N. */
+int mmg_cluster_centroids(const float* T, const long long* labels, int N, int D, int k, float* out, mmg_stream_t stream);
+
 /* ---- fp8 (OCP e4m3) forward GEMM path: BASELINE config C5 "ConvNeXt-base fp8 MFMA path" ---------------------------------
  * The reference has no reduced-precision path (its towers run torch fp32, mmgclip/networks/encoder.py:53,156); these replace
  * the same nn.Linear forwards of torchvision's CNBlock as mmg_gemm_nt_bf16 does, on v_mfma_f32_16x16x128_f8f6f4 (twice the

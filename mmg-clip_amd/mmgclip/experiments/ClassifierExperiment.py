@@ -68,10 +68,15 @@ class ClassifierExperiment:
 
         loss_cls = create_loss(self.config.loss.config.loss_name)
         use_global = comm is not None and _get(config, "distributed.global_loss", True)
+        # `loss.config.fused` / `loss.config.similarity_threshold` (AveragedMedicalCLIPLoss) are handed over when present
+        loss_kw = {k: _get(config, f"loss.config.{k}", None) for k in ("fused", "similarity_threshold")}
+        loss_kw = {k: v for k, v in loss_kw.items() if v is not None}
+        self._criterion_takes_comm = True
         try:
-            self.criterion = loss_cls(comm=comm if use_global else None).to(self.device)
-        except TypeError:
-            self.criterion = loss_cls().to(self.device)
+            self.criterion = loss_cls(comm=comm if use_global else None, **loss_kw).to(self.device)
+        except TypeError:                 # a criterion without `comm`: every rank has its local-batch loss (_grad_sync averages)
+            self._criterion_takes_comm = False
+            self.criterion = loss_cls(**loss_kw).to(self.device)
         logger.info(f"Using {self.criterion.__class__.__name__} loss.")
 
         lr, wd = self.config.optimizer.config.learning_rate, self.config.optimizer.config.weight_decay
@@ -131,13 +136,14 @@ class ClassifierExperiment:
     def _grad_sync(self):
         """GradSync over the tower arenas + every other trainable parameter; built once the arenas exist, i.e. after the first
         forward.  With the global-batch loss the gradients of the ranks are SUMMED (the loss carries 1/(2N) of the global mean);
-        with `distributed.global_loss: false` every rank has its own local-batch loss and the gradients are AVERAGED."""
+        with `distributed.global_loss: false`, or with a criterion that could not take `comm`, every rank has its own local-batch
+        loss and the gradients are AVERAGED."""
         if self._sync is None:
             from ..distributed import GradSync
             arenas = [t.arena for t in self._towers() if t.arena is not None and t.arena.any_trainable()]
             owned = {id(p) for a in arenas for p in a.params}
             extra = [p for p in self.model.parameters() if p.requires_grad and id(p) not in owned]
-            use_global = _get(self.config, "distributed.global_loss", True)
+            use_global = _get(self.config, "distributed.global_loss", True) and getattr(self, "_criterion_takes_comm", True)
             self._sync = GradSync(self.comm, arenas, extra, scale=1.0 if use_global else 1.0 / self.comm.world_size)
             for t in self._towers():
                 t.post_backward_hook = self._sync.reduce_arena_async
@@ -154,7 +160,9 @@ class ClassifierExperiment:
             if parallel:
                 for t in self._towers():
                     begin_step(t)
-            outputs = self.model(batch)
+            # a criterion that will not read the [n,n] logits (AveragedMedicalCLIPLoss on its fused path) is not given any
+            wants_logits = getattr(self.criterion, "needs_logits", True)
+            outputs = self.model(batch) if wants_logits else self.model(batch, materialize_logits=False)
             loss, labels = self.criterion(**outputs)
             sync = self._grad_sync() if parallel else None      # (installs the towers' post-backward hooks on first use)
             loss.backward()

@@ -210,6 +210,122 @@ def greedy_threshold_labels(sim, threshold):
     return labels, counts, int(k.item())
 
 
+class _HipAveragedBackend:
+    """The product arithmetic of the fused AveragedMedicalCLIPLoss: the entry points of csrc/averaged_head.hip plus the similarity
+    and clustering kernels the dense path already uses.  As with `_HipHeadBackend`, no product signature selects anything else;
+    tests/test_averaged_fused_cpu.py replaces this module attribute in its worker processes (gloo, CPU)."""
+
+    @staticmethod
+    def cluster(txt_all, threshold):
+        """(labels int64 [N], counts int32 [N], k) of the gathered text: the similarity exactly as
+        `AveragedMedicalCLIPLoss._mesaure_embeddings_similarity` forms it (a transient [N,N] fp32, no autograd), then
+        losses.py:148-162 as one kernel."""
+        _hip.require_gpu(txt_all)
+        e = L2Normalize.apply(txt_all.detach()).contiguous()
+        one = torch.ones(1, device=e.device)
+        _, _, sim = rows_forward(e, e, one, 0, True)
+        return greedy_threshold_labels(sim, threshold)
+
+    @staticmethod
+    def centroids(txt_all, labels, k):
+        N, D = txt_all.shape
+        out = torch.empty(k, D, device=txt_all.device, dtype=torch.float32)
+        call("mmg_cluster_centroids", ptr(txt_all), ptr(labels), N, D, k, ptr(out), stream())
+        return out
+
+    @staticmethod
+    def rows_forward(x_loc, y, scale, row_label):
+        _hip.require_gpu(x_loc, y, scale, row_label)
+        n_loc, D = x_loc.shape
+        lse = torch.empty(n_loc, device=x_loc.device, dtype=torch.float32)
+        pos = torch.empty(n_loc, device=x_loc.device, dtype=torch.float32)
+        call("mmg_clip_labelled_rows_fwd", ptr(x_loc), ptr(y), ptr(scale), ptr(row_label), n_loc, y.shape[0], D, ptr(lse), ptr(pos),
+             stream())
+        return lse, pos
+
+    loss_sum = staticmethod(_HipHeadBackend.loss_sum)
+
+    @staticmethod
+    def rows_backward_row(x_loc, y, scale, lse_row, row_label, gout, coef, dx, dscale):
+        """ROW product; `dx` None = a fresh buffer, else accumulated into; `dscale` (a [1] tensor or None) is accumulated."""
+        n_loc, D = x_loc.shape
+        acc = dx is not None
+        if dx is None:
+            dx = torch.empty_like(x_loc)
+        call("mmg_clip_labelled_rows_bwd_row", ptr(x_loc), ptr(y), ptr(scale), ptr(lse_row), ptr(row_label), ptr(gout), coef,
+             n_loc, y.shape[0], D, int(acc), ptr(dx), ptr(dscale), stream())
+        return dx
+
+    @staticmethod
+    def rows_backward_col(x_loc, y, scale, lse_col, col_label, row_key, key_off, counts, gout, coef, dx):
+        """COL product; `row_key` None = key_off + r; `counts` None = weight 1, else 1 / counts[key]."""
+        n_loc, D = x_loc.shape
+        acc = dx is not None
+        if dx is None:
+            dx = torch.empty_like(x_loc)
+        call("mmg_clip_labelled_rows_bwd_col", ptr(x_loc), ptr(y), ptr(scale), ptr(lse_col), ptr(col_label), ptr(row_key), key_off,
+             ptr(counts), 0 if counts is None else counts.shape[0], ptr(gout), coef, n_loc, y.shape[0], D, int(acc), ptr(dx), stream())
+        return dx
+
+
+class FusedAveragedLoss(torch.autograd.Function):
+    """AveragedMedicalCLIPLoss over (already L2-normalised) embeddings of the GLOBAL batch, no [n,N] logits (losses.py:164-216).
+
+    loss = 1/(2N) [ sum_i (lse1_i - s <I_i, Tbar_c(i)>) + sum_j (lse2_j - s <T_j, I_c(j)>) ]
+    c = greedy threshold labels of the gathered text, Tbar = cluster means of the text embeddings (the reference's column average
+    of s I T^T, by linearity), lse1 / lse2 the row log-sum-exps of s I Tbar^T and s T I^T.  The exchanges are FusedClipLoss's:
+    all-gather of the embeddings, all-gather of the two log-sum-exp vectors, all-reduce of the loss; every rank clusters the same
+    gathered bits with the same deterministic kernels, so no collective's shape depends on k.  Gradients are for the local rows
+    and complete locally; d loss / d scale is the local rows' share.  The labels carry no gradient.
+    Returns (loss, global cluster ids of the local rows)."""
+
+    @staticmethod
+    def forward(ctx, img, txt, scale, threshold, comm):
+        be = _HipAveragedBackend
+        img, txt = _f32c(img), _f32c(txt)
+        scale = _f32c(scale.reshape(1))
+        n_loc, D = img.shape
+        active = comm is not None and comm.active
+        if not active:
+            img_all, txt_all, off, N = img, txt, 0, n_loc
+        else:
+            img_all, txt_all = comm.all_gather_rows(img), comm.all_gather_rows(txt)
+            off, N = comm.rank * n_loc, n_loc * comm.world_size
+        labels, counts, k = be.cluster(txt_all, threshold)
+        cent = be.centroids(txt_all, labels, k)
+        c_loc = labels[off:off + n_loc].contiguous()
+        lse_i, pos_i = be.rows_forward(img, cent, scale, c_loc)
+        lse_t, pos_t = be.rows_forward(txt, img_all, scale, c_loc)
+        loss = be.loss_sum(lse_i, pos_i, lse_t, pos_t, 1.0 / (2.0 * N))
+        if active:
+            lse_i_all, lse_t_all = comm.all_gather_rows(lse_i), comm.all_gather_rows(lse_t)
+            loss = comm.all_reduce_sum(loss)
+        else:
+            lse_i_all, lse_t_all = lse_i, lse_t
+        ctx.save_for_backward(img, txt, scale, img_all, txt_all, cent, labels, counts, c_loc, lse_i, lse_t, lse_i_all, lse_t_all)
+        ctx.off, ctx.N, ctx.be = off, N, be
+        ctx.mark_non_differentiable(c_loc)
+        return loss.reshape(()), c_loc
+
+    @staticmethod
+    def backward(ctx, gout, _dlabels):
+        img, txt, scale, img_all, txt_all, cent, labels, counts, c_loc, lse_i, lse_t, lse_i_all, lse_t_all = ctx.saved_tensors
+        be, off = ctx.be, ctx.off
+        gout = _f32c(gout.reshape(1))
+        coef = 1.0 / (2.0 * ctx.N)
+        dscale = torch.zeros(1, device=img.device, dtype=torch.float32)
+        dimg = be.rows_backward_row(img, cent, scale, lse_i, c_loc, gout, coef, None, dscale)
+        dimg = be.rows_backward_col(img, txt_all, scale, lse_t_all, labels, None, off, None, gout, coef, dimg)
+        dtxt = be.rows_backward_row(txt, img_all, scale, lse_t, c_loc, gout, coef, None, dscale)
+        dtxt = be.rows_backward_col(cent[c_loc].contiguous(), img_all, scale, lse_i_all, labels, c_loc, 0, counts, gout, coef, dtxt)
+        return dimg, dtxt, dscale.reshape(()), None, None
+
+
+def fused_averaged_loss(image_embeddings, text_embeddings, logit_scale, threshold, comm=None):
+    """AveragedMedicalCLIPLoss on normalised embeddings -> (loss, labels_of_local_rows); `logit_scale` is the exponentiated scale."""
+    return FusedAveragedLoss.apply(image_embeddings, text_embeddings, logit_scale, float(threshold), comm)
+
+
 class ClusterMeanCols(torch.autograd.Function):
     """[n,N] logits -> [n,k] per-cluster column means (losses.py:164-186) and the matching gradient."""
 

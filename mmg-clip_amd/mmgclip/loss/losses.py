@@ -2,7 +2,7 @@
 on the fp32 MI355X head kernels.  All return `(loss: 0-d tensor, labels: int64 [n])`.
 
 `criterion(**outputs)` works exactly as in mmgclip/experiments/ClassifierExperiment.py:112.  When the model was run
-with `materialize_logits=False` the CLIP loss takes the fused path (no [n,n] matrices in HBM)."""
+with `materialize_logits=False` the CLIP loss and the averaged loss take their fused paths (no [n,n] logit matrices in HBM)."""
 import torch
 import torch.nn as nn
 
@@ -54,11 +54,26 @@ class AveragedMedicalCLIPLoss(nn.Module):
     as one kernel; the only host traffic is the 4-byte cluster count), the per-cluster column means and both cross-entropies.
     `_assign_labels` / `_average_logits` keep the reference's signatures (a list of labels in and out) for callers that use
     the helpers directly.
+
+    Two paths.  The dense one takes the model's materialised [n,n] logits (the reference's call).  The fused one
+    (`head.fused_averaged_loss`) runs from the normalised embeddings, puts no [n,N] logit matrix in HBM and, with a communicator,
+    is the loss of the GLOBAL batch: the clusters, the averaged columns and the text-side targets are those of all ranks' reports.
+    It is taken when the logits are absent, when `comm` is active, or when `fused` is true; `needs_logits` tells the caller
+    whether `forward` will read the logits at all.
     """
 
-    def __init__(self, similarity_threshold=0.65):
+    def __init__(self, similarity_threshold=0.65, comm=None, fused=None):
         super().__init__()
         self.similarity_threshold = similarity_threshold
+        self.comm = comm          # mmgclip.distributed.Comm for the global-batch loss (None = local batch)
+        self.fused = fused        # None / False: fused only when the logits are absent or comm is active
+
+    def _takes_fused_path(self, have_logits):
+        return (not have_logits) or (self.comm is not None and self.comm.active) or bool(self.fused)
+
+    @property
+    def needs_logits(self):
+        return not self._takes_fused_path(True)
 
     def _mesaure_embeddings_similarity(self, embeddings):
         e = head.L2Normalize.apply(embeddings.detach())
@@ -76,7 +91,9 @@ class AveragedMedicalCLIPLoss(nn.Module):
         counts = torch.bincount(labels, minlength=logits.shape[1]).to(torch.int32)
         return head.ClusterMeanCols.apply(logits, labels, counts, k)
 
-    def forward(self, image_embeddings, text_embeddings, logit_scale, logits_per_image, logits_per_text, **kwargs):
+    def forward(self, image_embeddings, text_embeddings, logit_scale, logits_per_image=None, logits_per_text=None, **kwargs):
+        if self._takes_fused_path(logits_per_image is not None and logits_per_text is not None):
+            return head.fused_averaged_loss(image_embeddings, text_embeddings, logit_scale, self.similarity_threshold, self.comm)
         sim = self._mesaure_embeddings_similarity(text_embeddings)
         labels, counts, k = head.greedy_threshold_labels(sim, self.similarity_threshold)
         averaged = head.ClusterMeanCols.apply(logits_per_image, labels, counts, k)
