@@ -386,11 +386,14 @@ static int launch_ln(const LNArgs& a, hipStream_t stream) {
     // in flight per wave.  Same-run A/B (tools/ln_ab.py, profiles/r03_ln_ab.txt): forward 498 -> 389 us at M = 1 M x 384 (3.2 -> 4.1 TB/s),
     // 213 -> 191 at 262 k x 768, 779 -> 745 at 4.2 M x 192; the BACKWARD got slower with it (652 -> 805, 1231 -> 1523, 321 -> 432 us: three
     // chunks of dgamma / dbeta accumulators and operands per lane) and keeps the round-2 selection.  MMG_LN_CH3=0: off (A/B).
-    static const int ch3_on = getenv("MMG_LN_CH3") ? atoi(getenv("MMG_LN_CH3")) : 1;
+    // Both knobs are read per call, so that one process can launch either selection (tests/test_layernorm_gpu.py).
+    const char* ch3_env = getenv("MMG_LN_CH3");
+    const int ch3_on = ch3_env ? atoi(ch3_env) : 1;
     const bool ch3 = !BWD && ch3_on && nch % 3 == 0 && (nch / 3 == 8 || nch / 3 == 16 || nch / 3 == 32 || nch / 3 == 64);
     if (ch3) { G = nch / 3; ch = 3; }
     // the image tower's widths on the plain kernels above (MMG_LN_PLAIN=0: off, A/B)
-    static const int plain_on = getenv("MMG_LN_PLAIN") ? atoi(getenv("MMG_LN_PLAIN")) : 1;
+    const char* plain_env = getenv("MMG_LN_PLAIN");
+    const int plain_on = plain_env ? atoi(plain_env) : 1;
     const int g3 = nch % 3 == 0 ? nch / 3 : 0;
     const bool plain = plain_on && (g3 == 4 || g3 == 8 || g3 == 16 || g3 == 32 || g3 == 64) && !a.x_f32 && !a.res && !a.y_fp8 && !a.yf && !a.add &&
                        (!BWD || (a.mean && a.rstd));
