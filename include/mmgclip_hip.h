@@ -185,6 +185,16 @@ int mmg_view_pool_bwd(const float* dout, const int* offsets, const int* argmax, 
  * multiples of P: the remainder rows / columns are ignored, as a stride-P convolution does. */
 int mmg_patchify(const float* img, void* out, int n, int Cin, int H, int W, int P, int Kp, int scale16,
                  mmg_stream_t stream);
+/* The same rows from raw pixels, with per-image augmentation in the gather (csrc/pixel_input.hip).  img: [n,Cin,H,W] of src_kind
+ * 0 = fp32 in [0,1], 1 = uint16, 2 = uint8.  geom (device, nullable = identity): int32 [n,4] = flags (bit0 flip x, bit1 flip y), ty, tx, 0;
+ * tone (device, nullable = none): fp32 [n,2] = gain, offset.  Canvas pixel (y,x) of image i, fp32 arithmetic without contraction:
+ *   ys = y - ty, xs = x - tx, inside = 0 <= ys < H && 0 <= xs < W;  flags&2: ys = H-1-ys;  flags&1: xs = W-1-xs   (flip over the full H, W)
+ *   r = inside ? img[i,c,ys,xs] : 0;  x01 = r | float(r)/65535 | float(r)/255;
+ *   tone && (gain,offset) != (1,0): x01 = min(max(gain*x01 + offset, 0), 1);  v = scale16 ? (x01*65535 - 32767.5)/32767.5 : x01;  out = bf16(v)
+ * Any ty / tx / flags is safe (the inside test guards the only read); no host copy of the tables is needed.  With fp32 input and NULL
+ * tables the result is mmg_patchify's, bit for bit.  Additive entry point: mmg_abi_version() stays 5. */
+int mmg_patchify_aug(const void* img, int src_kind, void* out, int n, int Cin, int H, int W, int P, int Kp, int scale16,
+                     const int* geom, const float* tone, mmg_stream_t stream);
 
 /* torch.optim.AdamW step over a flat fp32 buffer (mmgclip/experiments/ClassifierExperiment.py:74,118);
  * p_bf16 (nullable) receives the refreshed bf16 working copy.  step counts from 1. */

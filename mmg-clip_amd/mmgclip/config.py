@@ -4,7 +4,8 @@ offline: SURVEY.md §5).  Implements exactly the subset the reference's configs 
   * `defaults:` lists with `_self_`, list-valued group selections (`- optimizer:\\n    - adamw`), nested groups
     (`dataset/percentage`, `networks/dropout`), an option written with a `.yaml` suffix; no `@package` directives, so
     the group path is the config key (configs/train_binary_class_clf.yaml:1-25);
-  * `key=value` / `group=option` / `+key=value` command-line overrides;
+  * `key=value` / `group=option` / `+key=value` command-line overrides; `+group=option` for a group no defaults list names (Hydra's
+    append: `+networks/image_encoder/augment=mammo`), merged after the defaults;
   * interpolations `${a.b.c}`, `${now:%Y-%m-%d}`, `${hydra:run.dir}`.
 Returns a `Config` (dict with attribute access, like the AttrDict the reference wraps around OmegaConf: train.py:11-14).
 The dotted keys that were set by `key=value` overrides are kept beside it (`overridden_keys(cfg)`, not an item of the dict): an
@@ -106,6 +107,13 @@ def compose(config_dir, config_name, overrides=()):
             _merge(cfg, node)
     if not self_done:
         _merge(cfg, root)
+    listed = {next(iter(e)) for e in defaults if isinstance(e, dict)}
+    for group, opt in group_choice.items():             # `+group=option`: a group outside the defaults list, appended
+        if group not in listed:
+            name = opt[:-5] if str(opt).endswith(".yaml") else str(opt)
+            node = {}
+            _set_path(node, group.replace("/", "."), _load_yaml(os.path.join(config_dir, group, name + ".yaml")))
+            _merge(cfg, node)
     for k, v in key_over:
         _set_path(cfg, k, v)
     now = datetime.datetime.now()

@@ -2,7 +2,8 @@
 with the collate_fn's keys and dtypes (dataset.py:343-351 / :548-561) from seeded generators.
 
     image_features  fp32 [n,1,768,1,1]  |N(1, 0.4)|   (pre-extracted mode)        or
-    image           fp32 [n,Cin,H,W]    U[0,1)        (pixel encoders; image_size = an int for square images or an (H, W) pair)
+    image           fp32 [n,Cin,H,W]    U[0,1)        (pixel encoders; image_size = an int for square images or an (H, W) pair);
+                    pixel_dtype "uint16" / "uint8": round(x * 65535) / round(x * 255) of the same draws, as a 16- / 8-bit file stores them
     text_tokens     {input_ids, token_type_ids, attention_mask} int64 [n,S]: [CLS]=101 ... [SEP]=102, body U{1000..V-1},
                     pad 0, lengths U{8..S}
     image_label     int64 [n,1], image_id list[str], image_description list[str], prompt_labels list[dict]
@@ -43,17 +44,29 @@ def image_hw(image_size):
     return int(image_size), int(image_size)
 
 
+PIXEL_DTYPES = {"float32": (torch.float32, None), "uint16": (torch.uint16, 65535.0), "uint8": (torch.uint8, 255.0)}
+
+
+def as_pixel_dtype(x, pixel_dtype):
+    """fp32 pixels in [0, 1] -> the raw integers a 16- / 8-bit file would hold: round(x * 65535) as uint16, round(x * 255) as uint8."""
+    if pixel_dtype not in PIXEL_DTYPES:
+        raise ValueError(f"pixel_dtype must be one of {sorted(PIXEL_DTYPES)}, got {pixel_dtype!r}")
+    dtype, top = PIXEL_DTYPES[pixel_dtype]
+    return x if top is None else (x * top).round().to(torch.int32).to(dtype)
+
+
 def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab_size=28996, seed=42, with_impression=False,
-                    views_per_study=None, view_sizes=None):
+                    views_per_study=None, view_sizes=None, pixel_dtype="float32"):
+    as_pixel_dtype(torch.zeros(0), pixel_dtype)
     if views_per_study is not None:
-        return _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes)
+        return _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes, pixel_dtype)
     g = torch.Generator().manual_seed(seed)
     batch = {}
     if image_size is None:
         batch["image_features"] = (1.0 + 0.4 * torch.randn(n, 1, feature_dim, 1, 1, generator=g)).abs()
     else:
         H, W = image_hw(image_size)
-        batch["image"] = torch.rand(n, in_chans, H, W, generator=g)
+        batch["image"] = as_pixel_dtype(torch.rand(n, in_chans, H, W, generator=g), pixel_dtype)
     batch["text_tokens"] = synthetic_tokens(n, S, vocab_size, g)
     if with_impression:
         batch["image_impression_tokens"] = synthetic_tokens(n, S, vocab_size, g)
@@ -67,7 +80,7 @@ def synthetic_batch(n, S=77, image_size=None, in_chans=1, feature_dim=768, vocab
     return batch
 
 
-def _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes):
+def _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_impression, views_per_study, view_sizes, pixel_dtype="float32"):
     """n exams of pixels.  Tokens, labels and ids are those of `synthetic_batch(n, image_size=None, ...)` with the same seed (one report per
     exam); the view counts, sizes and pixels come from a second generator, so the draws of the plain batch are left as they are."""
     lo, hi = (int(v) for v in views_per_study)
@@ -84,7 +97,7 @@ def _synthetic_study_batch(n, S, image_size, in_chans, vocab_size, seed, with_im
     studies = []
     for k in counts:
         which = torch.randint(0, len(sizes), (k,), generator=g).tolist()
-        studies.append([torch.rand(in_chans, *sizes[j], generator=g) for j in which])
+        studies.append([as_pixel_dtype(torch.rand(in_chans, *sizes[j], generator=g), pixel_dtype) for j in which])
     return {"image": studies, **batch}
 
 

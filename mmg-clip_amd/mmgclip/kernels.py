@@ -221,10 +221,33 @@ def view_pool_bwd(dout, offsets, argmax, V, mode, out=None):
     return dx
 
 
-def patchify(img, P, Kp, scale16):
+PIXEL_KINDS = {torch.float32: 0, torch.uint16: 1, torch.uint8: 2}      # mmg_patchify_aug's src_kind
+
+
+def stack_images(images):
+    """torch.stack of [Cin, H, W] images; uint16 is storage only in torch (few ops take it), so those are stacked as their int16 views."""
+    if images[0].dtype == torch.uint16:
+        return torch.stack([t.view(torch.int16) for t in images]).view(torch.uint16)
+    return torch.stack(list(images))
+
+
+def patchify(img, P, Kp, scale16, geom=None, tone=None):
+    """img [n, Cin, H, W], fp32 in [0, 1] or raw uint16 / uint8 -> bf16 [n * (H // P) * (W // P), Kp] stem rows.  geom (int32 [n, 4]: flags,
+    ty, tx, 0) and tone (fp32 [n, 2]: gain, offset), on the device, apply flip -> shift -> fill -> tone per image (mmgclip/augment.py).
+    fp32 without tables is `mmg_patchify`, as ever; anything else `mmg_patchify_aug` (csrc/pixel_input.hip)."""
     n, Cin, H, W = img.shape
+    if img.dtype not in PIXEL_KINDS:
+        raise TypeError(f"pixels must be float32 in [0, 1], uint16 or uint8, got {img.dtype}")
+    assert img.is_contiguous(), "pixels must be contiguous [n, Cin, H, W]"
+    _hip.require_gpu(img, geom, tone)
     out = torch.empty(n * (H // P) * (W // P), Kp, device=img.device, dtype=BF16)
-    call("mmg_patchify", ptr(img), ptr(out), n, Cin, H, W, P, Kp, 1 if scale16 else 0, stream())
+    if img.dtype == torch.float32 and geom is None and tone is None:
+        call("mmg_patchify", ptr(img), ptr(out), n, Cin, H, W, P, Kp, 1 if scale16 else 0, stream())
+        return out
+    assert geom is None or (geom.dtype == torch.int32 and geom.is_contiguous() and tuple(geom.shape) == (n, 4)), "geom: int32 [n, 4]"
+    assert tone is None or (tone.dtype == torch.float32 and tone.is_contiguous() and tuple(tone.shape) == (n, 2)), "tone: fp32 [n, 2]"
+    call("mmg_patchify_aug", ptr(img), PIXEL_KINDS[img.dtype], ptr(out), n, Cin, H, W, P, Kp, 1 if scale16 else 0, ptr(geom), ptr(tone),
+         stream())
     return out
 
 

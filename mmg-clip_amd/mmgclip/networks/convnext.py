@@ -39,7 +39,7 @@ from .._hip import call, ptr, stream
 from ..params import backward_finished, last_backward
 from . import convnext_sd as SD
 from .convnext_plan import BlockSaved, Knobs, decide_saves, fused_forward, plan_block, saving_form
-from .tower import Tower, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
+from .tower import Tower, as_pixels, augment_tables, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
 
 CONFIGS = {
     "tiny": dict(depths=(3, 3, 9, 3), dims=(96, 192, 384, 768)),
@@ -100,11 +100,14 @@ class _TorchvisionLayout(nn.Module):
 
 
 class ConvNextTower(Tower):
-    """pixels fp32 [n, Cin, H, W] in [0,1] (scale16=True applies the reference's 16-bit scaling) -> features [n, dims[-1]]."""
+    """pixels [n, Cin, H, W], fp32 in [0,1] or raw uint16 / uint8 (scale16=True applies the reference's 16-bit scaling) -> features
+    [n, dims[-1]].  augment (None | AugmentSpec | mapping, mmgclip/augment.py): seeded flip / shift / tone inside the stem's patchify, in
+    training mode only."""
 
     def __init__(self, variant="tiny", in_chans=1, scale16=True, micro_batch=64, fused_mlp=None, checkpoint=False, fp8=False,
-                 fp8_min_channels=None, stochastic_depth_prob=0.0):
+                 fp8_min_channels=None, stochastic_depth_prob=0.0, augment=None):
         super().__init__()
+        self.set_augment(augment)
         # torchvision's recipes: 0.1 (tiny), 0.4 (small), 0.5 (base); block b of B drops a sample with p_b = rate * b / (B - 1).  Acts in
         # training mode only, with or without gradients; 0 is the path without it, bit for bit
         self.stochastic_depth_prob = SD.check_rate(stochastic_depth_prob)
@@ -267,12 +270,12 @@ class ConvNextTower(Tower):
         return xn, BlockSaved(x, d, mean, rstd, hpre, aux_kind, ln if keep_ln else None, g if keep_g else None, bwd)
 
     # ---- forward / backward over one micro-batch -----------------------------------------------------------
-    def _forward_mb(self, img, plan, dec, sched=None):
+    def _forward_mb(self, img, plan, dec, sched=None, tabs=None):
         """plan: the tower's BlockPlans as the recorded forward this pass belongs to read them; dec: that forward's SaveDecision, or None
         when this pass saves nothing (no gradient wanted, or a checkpointed micro-batch whose forward runs again in the backward).
         sched: this micro-batch's stochastic-depth Schedule (convnext_sd.schedule) or None.  With one, the features leave in the order
         sched.perm (the caller routes them back), and a block that keeps n_k of the n images runs on the first n_k after the schedule's
-        swaps; its record holds views of that prefix."""
+        swaps; its record holds views of that prefix.  tabs: this micro-batch's augmentation tables (geom, tone) on the device, or None."""
         f, wc = self.model.features, self._wc
         save = dec is not None
         n, _, H, W = img.shape
@@ -286,7 +289,7 @@ class ConvNextTower(Tower):
                 table = (torch.tensor(sched.table, dtype=torch.int32, device=img.device), host)
             saved["sd"] = (steps, table)
         b = 0
-        p0 = K.patchify(img, 4, self.kp, self.scale16)
+        p0 = K.patchify(img, 4, self.kp, self.scale16, *(tabs or (None, None)))
         s0 = L.gemm_nt(p0, wc["stem.w"], bias=f[0][0].bias.data)
         x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
         if save:
@@ -485,9 +488,10 @@ class ConvNextTower(Tower):
         return h, w
 
     def forward(self, images, sample_ids=None):
-        """images: fp32 [n, Cin, H, W] (any H, W >= 32), or a list / tuple of [Cin, H_i, W_i] tensors whose sizes may differ: those are grouped by
-        size (`group_by_size`), every group runs in micro-batches of its own, and row i of the result belongs to images[i].
-        sample_ids (stochastic depth only): the number under which image i draws its masks, default i - its position in this input."""
+        """images: [n, Cin, H, W] (any H, W >= 32; fp32 in [0,1], or raw uint16 / uint8, which stay as they are), or a list / tuple of
+        [Cin, H_i, W_i] tensors whose sizes may differ: those are grouped by size (`group_by_size`), every group runs in micro-batches of its
+        own, and row i of the result belongs to images[i].
+        sample_ids (stochastic depth and augmentation): the number under which image i draws, default i - its position in this input."""
         plan = None
         if isinstance(images, (list, tuple)):
             if not images or any(not torch.is_tensor(t) or t.dim() != 3 for t in images):
@@ -514,9 +518,10 @@ class ConvNextTower(Tower):
             if len(ids) != len(images):
                 raise ValueError(f"sample_ids names {len(ids)} images, the input holds {len(images)}")
             seed = (seed, ids)
+        aug = self._draw_augment(len(images), sample_ids)       # one draw per forward; the rows go with the forward's record
         if plan is None:
-            return _ConvNextFn.apply(self, images.float().contiguous(), anchor, None, seed)
-        return _ConvNextFn.apply(self, [t.float() for t in images], anchor, plan, seed)
+            return _ConvNextFn.apply(self, as_pixels(images).contiguous(), anchor, None, seed, aug)
+        return _ConvNextFn.apply(self, [as_pixels(t) for t in images], anchor, plan, seed, aug)
 
 
 def group_by_size(sizes, micro_batch):
@@ -538,8 +543,9 @@ def group_by_size(sizes, micro_batch):
 
 class _ConvNextFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tower, images, anchor, plan, sd_seed=None):
-        """sd_seed: None, or (seed, sample ids) of a forward that applies stochastic depth."""
+    def forward(ctx, tower, images, anchor, plan, sd_seed=None, aug=None):
+        """sd_seed: None, or (seed, sample ids) of a forward that applies stochastic depth; aug: None, or the (geom rows, tone rows) of a
+        forward that augments (Tower._draw_augment)."""
         tower._refresh_working_copies()
         save = anchor is not None
         mb = tower.micro_batch
@@ -552,7 +558,7 @@ class _ConvNextFn(torch.autograd.Function):
         else:                               # images of several sizes: one [k, Cin, H, W] tensor per group-micro-batch, built when it is needed
             count, device = len(images), images[0].device
             mbs = plan[0]
-            parts = [(lambda idx=idx: torch.stack([images[j] for j in idx]).contiguous()) for idx in plan[0]]
+            parts = [(lambda idx=idx: K.stack_images([images[j] for j in idx]).contiguous()) for idx in plan[0]]
             by_size = {}
             for idx in plan[0]:
                 hw = tuple(images[idx[0]].shape[-2:])
@@ -569,21 +575,27 @@ class _ConvNextFn(torch.autograd.Function):
             dec = tower._decide_saves(*alive[0], device, ckpt=ckpt and len(parts) > 1, more=alive[1:])
             tower.save_ln, tower.save_gelu, tower.fp8_bwd_now = dec         # (the latest forward's, for whoever reports them: bench.py)
         inverse = plan[1] if plan is not None else list(range(count))
+        # augmentation: row i of the tables belongs to input image i; ONE upload in processing order, a slice per micro-batch, carried
+        # along with the pixels like the schedules below, so a checkpointed recomputation reads the same rows
+        tabs = augment_tables(aug, mbs, device) if aug is not None else [None] * len(mbs)
         if sd_seed is not None:
             # stochastic depth: the mask of a sample is a function of (seed, block, its index in the INPUT); every micro-batch gets its
             # schedule here, once, and carries it along with its pixels (a part is opaque to forward_parts / backward_parts), so the
             # recomputation of a checkpointed part executes the same record
             rates = SD.block_rates(tower.stochastic_depth_prob, tower.depths)
             scheds = [SD.schedule(SD.keep_matrix(sd_seed[0], [sd_seed[1][i] for i in idx], rates)) for idx in mbs]
-            parts = [(lambda part=part, sch=sch: (part(), sch)) for part, sch in zip(parts, scheds)]
+            parts = [(lambda part=part, sch=sch, tab=tab: (part(), sch, tab)) for part, sch, tab in zip(parts, scheds, tabs)]
             inverse = SD.processing_order(mbs, scheds)[1]
-            run = lambda x, saving: tower._forward_mb(x[0], blocks, dec if saving else None, x[1])      # noqa: E731
+            run = lambda x, saving: tower._forward_mb(x[0], blocks, dec if saving else None, x[1], x[2])      # noqa: E731
+        elif aug is not None:
+            parts = [(lambda part=part, tab=tab: (part(), None, tab)) for part, tab in zip(parts, tabs)]
+            run = lambda x, saving: tower._forward_mb(x[0], blocks, dec if saving else None, None, x[2])      # noqa: E731
         else:
             run = lambda pix, saving: tower._forward_mb(pix, blocks, dec if saving else None)           # noqa: E731
         out, parts = forward_parts(parts, run, ckpt)
         ctx.tower, ctx.parts = tower, parts if save else None
         ctx.plan, ctx.decision = blocks, dec
-        ctx.inverse, ctx.sd = None, sd_seed is not None
+        ctx.inverse, ctx.sd = None, sd_seed is not None or aug is not None      # (sd: a part is (pixels, schedule, tables))
         if inverse != list(range(count)):
             ctx.inverse = torch.tensor(inverse, device=device)
             out = out.index_select(0, ctx.inverse)             # processing order -> input order
@@ -600,8 +612,8 @@ class _ConvNextFn(torch.autograd.Function):
 
         def bwd(d, saved, final):            # final: the GEMM-shaped temporaries are folded, and (the step's last backward) announced
             tower._backward_mb(d, saved, tmp, final=final, announce=final and last_backward(tower))
-        again = (lambda x: tower._forward_mb(x[0], ctx.plan, ctx.decision, x[1])[1]) if ctx.sd else \
+        again = (lambda x: tower._forward_mb(x[0], ctx.plan, ctx.decision, x[1], x[2])[1]) if ctx.sd else \
             (lambda pix: tower._forward_mb(pix, ctx.plan, ctx.decision)[1])
         backward_parts(ctx.parts, dfeat, again, bwd)
         backward_finished(tower)
-        return None, None, None, None, None
+        return None, None, None, None, None, None

@@ -124,6 +124,8 @@ class DropSeeds:
     `seeding(config.base.seed)` reproduces a run, torch's global generators are never consumed, and every data-parallel rank draws its own
     masks for its own samples."""
 
+    ADD = 0xD6E8FEB86659FD93            # the stream's additive constant (mmgclip/augment.py's AugmentSeeds has another)
+
     def __init__(self):
         self._gen = self._epoch = None
 
@@ -137,7 +139,7 @@ class DropSeeds:
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             rank = torch.distributed.get_rank()
         # splitmix-style fold of (seed, rank) as in BertTower.reseed_dropout, with another additive constant: an unrelated stream
-        mixed = (int(seed) * 0x9E3779B97F4A7C15 + (rank + 1) * 0xBF58476D1CE4E5B9 + 0xD6E8FEB86659FD93) & 0x7FFFFFFFFFFFFFFF
+        mixed = (int(seed) * 0x9E3779B97F4A7C15 + (rank + 1) * 0xBF58476D1CE4E5B9 + self.ADD) & 0x7FFFFFFFFFFFFFFF
         self._gen = torch.Generator().manual_seed(mixed)
         self._epoch = epoch
 

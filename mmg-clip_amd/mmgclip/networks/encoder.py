@@ -7,8 +7,8 @@ HIP towers (convnext.py / bert.py).
                      and raises on construction.
   BertEncoder       HF-layout BERT; `forward(x: mapping) -> last_hidden_state [B,S,H]`; frozen by default as in the
                     reference (encoder.py:141-142).
-New in-graph image encoders (SURVEY.md §7 decision 1): ConvNextTinyEncoder, ConvNextBaseEncoder — take pixels: one [n,Cin,H,W]
-tensor of any H, W >= 32, or a list of [Cin,H_i,W_i] images of different sizes (convnext.py); ViTB16Encoder and ResNet50Encoder reject a list.
+New in-graph image encoders (SURVEY.md §7 decision 1): ConvNextTinyEncoder, ConvNextBaseEncoder — take pixels (fp32 in [0,1], or raw
+uint16 / uint8; `augment`: seeded flip / shift / tone in training mode, mmgclip/augment.py): one [n,Cin,H,W] tensor of any H, W >= 32, or a list of [Cin,H_i,W_i] images of different sizes (convnext.py); ViTB16Encoder and ResNet50Encoder reject a list.
 """
 import json
 import os
@@ -88,9 +88,10 @@ class _ConvNextEncoder(ConvNextTower):
     VARIANT = "tiny"
 
     def __init__(self, pretrained=None, image_features_dimension=None, in_chans=1, scale16=True, micro_batch=64, freeze=False,
-                 checkpoint=False, fp8=False, stochastic_depth_prob=0.0):
+                 checkpoint=False, fp8=False, stochastic_depth_prob=0.0, augment=None):
+        # augment: networks.image_encoder.augment - {hflip, vflip, max_shift, gain: [lo, hi], offset: [lo, hi]}; absent / null: none
         super().__init__(self.VARIANT, in_chans=in_chans, scale16=scale16, micro_batch=micro_batch, checkpoint=checkpoint,
-                         fp8=fp8, stochastic_depth_prob=stochastic_depth_prob)
+                         fp8=fp8, stochastic_depth_prob=stochastic_depth_prob, augment=augment)
         if isinstance(pretrained, str) and os.path.isfile(pretrained):
             sd = _load_state_file(pretrained)
             sd = {k[len("model."):] if k.startswith("model.") else k: v for k, v in sd.items()}
@@ -116,9 +117,9 @@ class ViTB16Encoder(ViTTower):
     """ViT-B/16 on raw pixels (BASELINE config C4; torchvision `vit_b_16` state-dict layout, class-token pooling)."""
 
     def __init__(self, pretrained=None, image_features_dimension=None, in_chans=1, scale16=True, micro_batch=256, freeze=False,
-                 image_size=224, layers=12, checkpoint=False):
+                 image_size=224, layers=12, checkpoint=False, augment=None):
         super().__init__(image_size=image_size, in_chans=in_chans, layers=layers, scale16=scale16, micro_batch=micro_batch,
-                         checkpoint=checkpoint)
+                         checkpoint=checkpoint, augment=augment)
         if isinstance(pretrained, str) and os.path.isfile(pretrained):
             sd = _load_state_file(pretrained)
             self.model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("heads.")}, strict=True)
@@ -129,11 +130,11 @@ class ViTB16Encoder(ViTTower):
                 p.requires_grad = False
         logger.info("Initializing 'ViTB16Encoder' as the image encoder.")
 
-    def forward(self, images):
+    def forward(self, images, sample_ids=None):
         if isinstance(images, (list, tuple)):
             raise ValueError(f"ViTB16Encoder takes one [n, Cin, {self.image_size}, {self.image_size}] tensor (learned positions fix the size), "
                              "not a list of images")
-        return super().forward(images)
+        return super().forward(images, sample_ids)
 
 
 class BertEncoder(BertTower):

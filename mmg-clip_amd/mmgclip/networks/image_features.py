@@ -18,13 +18,21 @@ from .encoder import ConvNextTiny
 from .view_pool import normalize_method, pool_views
 
 
-def load_image(path):
-    """PIL image -> fp32 [1, H, W] in [0, 1] (what torchvision.transforms.ToTensor yields for 8- and 16-bit PNGs)."""
+def load_image(path, raw=False):
+    """PIL image -> fp32 [1, H, W] in [0, 1] (what torchvision.transforms.ToTensor yields for 8- and 16-bit PNGs).
+    raw=True: the integer array unconverted - uint8 / uint16 [1, H, W] as the file stores it, which the pixel towers read directly (half / a
+    quarter of the bytes; PIL hands a 16-bit PNG over as uint16 or int32, both in [0, 65535]).  A file that holds neither raises."""
     from PIL import Image
     img = Image.open(path)
     arr = np.array(img)
     if arr.ndim == 3:
         arr = arr[..., 0]
+    if raw:
+        if arr.dtype == np.uint8:
+            return torch.from_numpy(np.ascontiguousarray(arr))[None]
+        if arr.dtype in (np.uint16, np.int32) and arr.min() >= 0 and arr.max() <= 65535:
+            return torch.from_numpy(np.ascontiguousarray(arr.astype(np.uint16)))[None]
+        raise ValueError(f"{path}: raw=True needs 8- or 16-bit integer pixels, the file holds {arr.dtype}")
     if arr.dtype == np.uint8:
         x = arr.astype(np.float32) / 255.0
     elif arr.dtype in (np.uint16, np.int32, np.int16):

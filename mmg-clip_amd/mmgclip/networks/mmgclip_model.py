@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import head
+from ..kernels import stack_images
 from ..utils.logger import logger
 from .bert import EosPool
 from .network_controller import getNetworkClass
@@ -57,7 +58,7 @@ class MMGCLIP(nn.Module):
                 pretrained=_get(ie, "pretrained_path"), image_features_dimension=None if joined else ie.image_features_dimension,
                 in_chans=_get(ie, "in_chans", 1), scale16=_get(ie, "scale16", True), micro_batch=_get(ie, "micro_batch", 64),
                 freeze=_get(ie, "freeze", False),
-                checkpoint=_get(ie, "checkpoint", False),
+                checkpoint=_get(ie, "checkpoint", False), augment=_get(ie, "augment"),
                 **({"image_size": _get(ie, "image_size", 224)} if enc_name == "ViTB16Encoder" else
                    {"fp8": _get(ie, "fp8", False), "stochastic_depth_prob": _get(ie, "stochastic_depth_prob", 0.0)})).to(self.device)
             logger.info(f"Using {self.image_encoder.__class__.__name__}")
@@ -122,7 +123,7 @@ class MMGCLIP(nn.Module):
             counts = [len(s) for s in pix]
             views = [v for s in pix for v in s]
             if len({tuple(v.shape) for v in views}) == 1:
-                views = torch.stack(list(views))                    # every view of one size: the towers' 4-D path
+                views = stack_images(list(views))                   # every view of one size: the towers' 4-D path (any pixel dtype)
             elif name == "ViTB16Encoder":
                 raise ValueError(f"ViTB16Encoder needs every view at {self.image_encoder.image_size}x{self.image_encoder.image_size} "
                                  f"(learned positions fix the size), got views of the sizes {sorted({tuple(v.shape[-2:]) for v in views})}")

@@ -13,6 +13,8 @@ import os
 import torch
 import torch.nn as nn
 
+from .. import augment as AUG
+from .. import kernels as K
 from .._hip import call, ptr, stream
 from ..params import ParamArena, note_forward, stream_anchor
 
@@ -22,6 +24,10 @@ class Tower(nn.Module):
         super().__init__()
         self._arena = self._wc = self._wc_version = None
         self.post_backward_hook = None      # called with the arena once this tower's gradients are complete
+        # pixel towers: seeded augmentation inside the stem's patchify (mmgclip/augment.py); acts in training mode only
+        self.augment = None
+        self.next_augment_seed = None       # tests: force the seed of the next forward that augments
+        self._augment_seeds = AUG.AugmentSeeds()
 
     @property
     def arena(self):
@@ -54,6 +60,27 @@ class Tower(nn.Module):
         self._wc = self._build_working_copies()
         self._wc_version = v
 
+    def set_augment(self, augment):
+        """None | AugmentSpec | mapping (networks.image_encoder.augment) -> self.augment, validated."""
+        self.augment = AUG.make_spec(augment)
+
+    def augment_active(self):
+        return self.training and self.augment is not None
+
+    def _draw_augment(self, count, sample_ids):
+        """One draw per forward: -> (geom rows, tone rows) of its `count` images, or None when no augmentation acts.  sample_ids: the number
+        under which image i draws, default i - its position in this input."""
+        if not self.augment_active():
+            return None
+        if self.next_augment_seed is not None:
+            seed, self.next_augment_seed = int(self.next_augment_seed), None
+        else:
+            seed = self._augment_seeds.draw()
+        ids = list(range(count)) if sample_ids is None else [int(i) for i in sample_ids]
+        if len(ids) != count:
+            raise ValueError(f"sample_ids names {len(ids)} images, the input holds {count}")
+        return AUG.draw(self.augment, seed, ids)
+
     def _record_forward(self, device, wants_grad=True):
         """Start of a forward on `device` (the input's): -> the stream anchor the tower's autograd Function takes when this forward is
         recorded for a backward, else None."""
@@ -61,6 +88,26 @@ class Tower(nn.Module):
         needs_grad = torch.is_grad_enabled() and wants_grad and self._arena.any_trainable()
         note_forward(self, needs_grad)
         return stream_anchor(self, device) if needs_grad else None
+
+
+# ---- pixels in ------------------------------------------------------------------------------------------------------------------------
+def as_pixels(t):
+    """fp32 in [0, 1], or raw uint16 / uint8, stay as they are (the stem's patchify reads all three); anything else becomes fp32."""
+    return t if t.dtype in K.PIXEL_KINDS else t.float()
+
+
+def augment_tables(rows, micro_batches, device):
+    """rows: Tower._draw_augment's (geom, tone), one row per input image; micro_batches: per micro-batch the input indices of its images.
+    -> per micro-batch (geom int32 [k, 4], tone fp32 [k, 2]) on `device`: the rows are put into processing order on the host and
+    uploaded ONCE, every micro-batch gets a slice (a view) of that upload."""
+    order = [i for idx in micro_batches for i in idx]
+    geom = torch.tensor([rows[0][i] for i in order], dtype=torch.int32).reshape(-1, 4).to(device)
+    tone = torch.tensor([rows[1][i] for i in order], dtype=torch.float32).reshape(-1, 2).to(device)
+    out, start = [], 0
+    for idx in micro_batches:
+        out.append((geom[start:start + len(idx)], tone[start:start + len(idx)]))
+        start += len(idx)
+    return out
 
 
 # ---- micro-batches and gradient checkpointing ---------------------------------------------------------------------------------------

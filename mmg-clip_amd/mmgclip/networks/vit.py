@@ -18,7 +18,7 @@ from .. import kernels as K
 from .. import linalg as L
 from .._hip import call, ptr, stream
 from ..params import backward_finished
-from .tower import Tower, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
+from .tower import Tower, as_pixels, augment_tables, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
 
 LN_EPS = 1e-6
 
@@ -54,11 +54,12 @@ def _tv_layout(image_size, in_chans, hidden, layers, mlp_dim, patch):
 
 
 class ViTTower(Tower):
-    """pixels fp32 [n, Cin, H, W] -> class-token features [n, hidden]."""
+    """pixels [n, Cin, H, W], fp32 in [0,1] or raw uint16 / uint8 -> class-token features [n, hidden].  augment: as ConvNextTower's."""
 
     def __init__(self, image_size=224, in_chans=1, hidden=768, layers=12, heads=12, mlp_dim=3072, patch=16, scale16=True,
-                 micro_batch=256, checkpoint=False):
+                 micro_batch=256, checkpoint=False, augment=None):
         super().__init__()
+        self.set_augment(augment)
         self.checkpoint = checkpoint        # keep only each micro-batch's pixels, re-run its forward inside its backward
         assert hidden == 64 * heads, "the attention kernel is specialised for head_dim 64"
         self.image_size, self.in_chans, self.hidden, self.layers, self.heads = image_size, in_chans, hidden, layers, heads
@@ -83,10 +84,10 @@ class ViTTower(Tower):
                 wc[f"{i}.{tag}t"] = K.transpose_cast_bf16(wt)
         return wc
 
-    def _forward_mb(self, img, save):
+    def _forward_mb(self, img, save, tabs=None):
         wc, H, S, heads = self._wc, self.hidden, self.seq, self.heads
         B = img.shape[0]
-        p0 = K.patchify(img, self.patch, self.kp, self.scale16)
+        p0 = K.patchify(img, self.patch, self.kp, self.scale16, *(tabs or (None, None)))
         tok = L.gemm_nt(p0, wc["conv"], bias=self.model.conv_proj.bias.data)
         x = torch.empty(B * S, H, device=img.device, dtype=torch.bfloat16)
         call("mmg_vit_assemble_fwd", ptr(tok), ptr(wc["cls"]), ptr(wc["pos"]), ptr(x), B, S, H, stream())
@@ -159,21 +160,35 @@ class ViTTower(Tower):
         L.gemm_tn_acc(dtok, saved["p0"], tmp, colsum=A.g("conv_proj.bias"))
         fold_conv_grad(tmp, A.g("conv_proj.weight"), H, self.in_chans, self.patch, self.patch)
 
-    def forward(self, images):
+    def forward(self, images, sample_ids=None):
+        """images: [n, Cin, S, S] (fp32 in [0,1], or raw uint16 / uint8), or a list of [Cin, S, S] images, S = image_size.
+        sample_ids (augmentation): the number under which image i draws, default i - its position in this input."""
+        if isinstance(images, (list, tuple)):
+            if not images or any(not torch.is_tensor(t) or t.dim() != 3 for t in images):
+                raise ValueError("a list of images must hold [Cin, H, W] tensors")
+            if len({tuple(t.shape) for t in images}) != 1:
+                raise ValueError(f"ViT was built for {self.image_size}x{self.image_size} inputs (learned positions): every image of a list must "
+                                 f"have that size, got {sorted({tuple(t.shape[-2:]) for t in images})}")
+            images = K.stack_images([as_pixels(t) for t in images])
         _hip.require_gpu(images)
         if images.shape[-1] != self.image_size or images.shape[-2] != self.image_size:
             raise ValueError(f"ViT was built for {self.image_size}x{self.image_size} inputs (learned positions), got {tuple(images.shape)}")
-        return _ViTFn.apply(self, images.float().contiguous(), self._record_forward(images.device))
+        anchor = self._record_forward(images.device)
+        return _ViTFn.apply(self, as_pixels(images).contiguous(), anchor, self._draw_augment(images.shape[0], sample_ids))
 
 
 class _ViTFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tower, images, anchor):
+    def forward(ctx, tower, images, anchor, aug=None):
+        """aug: None, or the (geom rows, tone rows) of a forward that augments (Tower._draw_augment): uploaded once, a slice per micro-batch,
+        kept with the part so that a checkpointed recomputation reads the same rows."""
         tower._refresh_working_copies()
         save = anchor is not None
-        mb = tower.micro_batch
-        parts = [(lambda i=i: images[i:i + mb]) for i in range(0, images.shape[0], mb)]
-        out, parts = forward_parts(parts, lambda pix, saving: tower._forward_mb(pix, save and saving), save and tower.checkpoint)
+        mb, count = tower.micro_batch, images.shape[0]
+        starts = range(0, count, mb)
+        tabs = augment_tables(aug, [list(range(i, min(i + mb, count))) for i in starts], images.device) if aug is not None else [None] * len(starts)
+        parts = [(lambda i=i, tab=tab: (images[i:i + mb], tab)) for i, tab in zip(starts, tabs)]
+        out, parts = forward_parts(parts, lambda x, saving: tower._forward_mb(x[0], save and saving, x[1]), save and tower.checkpoint)
         ctx.tower, ctx.parts = tower, parts if save else None
         return out
 
@@ -182,6 +197,6 @@ class _ViTFn(torch.autograd.Function):
         tower = ctx.tower
         tower._arena.prepare_grads()
         dfeat = dfeat.float().contiguous()
-        backward_parts(ctx.parts, dfeat, lambda pix: tower._forward_mb(pix, True)[1], lambda d, saved, last: tower._backward_mb(d, saved))
+        backward_parts(ctx.parts, dfeat, lambda x: tower._forward_mb(x[0], True, x[1])[1], lambda d, saved, last: tower._backward_mb(d, saved))
         backward_finished(tower)
-        return None, None, None
+        return None, None, None, None

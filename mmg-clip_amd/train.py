@@ -33,6 +33,8 @@ def build_loaders(cfg, rank=0):
     if pixels:
         size = _get(cfg, "networks.image_encoder.image_size", 224)           # an int, or [H, W] for rectangular images
         kw.update(image_size=tuple(size) if isinstance(size, (list, tuple)) else size, in_chans=_get(cfg, "networks.image_encoder.in_chans", 1))
+        if _get(cfg, "dataset.config.pixel_dtype") is not None:              # "uint16" / "uint8": raw pixels, as the files store them
+            kw.update(pixel_dtype=str(_get(cfg, "dataset.config.pixel_dtype")))
         if _get(cfg, "dataset.config.views_from_pixels", False):             # exams: every sample a list of views, pooled inside the model
             kw.update(views_per_study=tuple(_get(cfg, "dataset.config.synthetic_views_per_study", (1, 4))),
                       view_sizes=[tuple(hw) for hw in _get(cfg, "dataset.config.synthetic_view_sizes", None) or [image_hw(kw["image_size"])]])
