@@ -149,6 +149,15 @@ int mmg_layernorm_bwd_f32(const void* dy, int lddy, const float* x, int ldx, con
 int mmg_layernorm_bwd(const void* dy, int lddy, const void* x, int ldx, const float* mean, const float* rstd,
                       const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C, int patch,
                       int H, int W, const void* add, int ldadd, mmg_stream_t stream);
+/* What a LayerNorm entry point WOULD launch, without launching: the plan its host layer makes (csrc/layernorm_plan.h; all five entry
+ * points validate, make one plan and launch the kernel it names) as text - the exact mmg_last_kernel() spelling, then
+ * " grid=N block=256 lds=B nt=0|1" (B = dynamic LDS bytes, nt = streaming stores: outputs of 256 MiB and more, mmg_layernorm_fwd / _bwd
+ * only).  door: 0 mmg_layernorm_fwd, 1 _fwd_f32, 2 _fwd_fp8, 3 _bwd, 4 _bwd_f32; res, yf (door 1), add (doors 3, 4): that optional
+ * operand is given; contiguous operands, not patchified (neither changes a plan).  MMG_LN_PLAIN / MMG_LN_CH3 are honoured as by a launch.
+ * A shape the entry point would reject gives "" and sets mmg_last_error() to that entry point's message.  The string belongs to the
+ * calling thread and is valid until its next call; no GPU is needed.  No reference counterpart (diagnostics;
+ * tests/test_layernorm_plan_cpu.py pins kernel selection with it).  Additive entry point: mmg_abi_version() stays 5. */
+const char* mmg_layernorm_plan(int door, int M, int C, int res, int yf, int add);
 
 /* y = GELU(x) elementwise, bf16, n % 8 == 0 (rebuilds the FFN activation in the backward pass). */
 int mmg_gelu_fwd_bf16(const void* x, void* y, long long n, mmg_stream_t stream);

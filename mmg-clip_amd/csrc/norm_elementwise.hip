@@ -9,10 +9,10 @@
 //   input scaling x*65535, (x-32767.5)/32767.5               (mmgclip/networks/image_features.py:95-99)
 //   torch.optim.AdamW                                        (mmgclip/experiments/ClassifierExperiment.py:74,118)
 #include "common.h"
-#include <stdlib.h>
+#include "layernorm_plan.h"
 
 // ---------------------------------------------------------------------------------------------
-// LayerNorm over the last dim C of a bf16 [M,C] matrix.  A row is owned by a group of G lanes
+// LayerNorm over the last dim C of a bf16 [M,C] matrix (LNArgs: layernorm_plan.h).  A row is owned by a group of G lanes
 // (G = power of two >= C/8, <= 64), 64/G rows per wave, CH 16-byte chunks per lane.
 // `patch` != 0 : the normalised row m = (n,h,w) is written to (read from, in the backward) the 2x2-patchified
 // position  row (n, h/2, w/2), columns ((h&1)*2 + (w&1))*C ..  of a [M/4, 4C] matrix, so that the following
@@ -21,24 +21,6 @@
 // the forward writes nothing for them, the backward reads no dy for them (its load is clamped to row 0 and zero is selected),
 // gives them dx = 0 (+ `add`) and keeps them out of dgamma / dbeta; their lanes still take part in every shuffle and barrier.
 // ---------------------------------------------------------------------------------------------
-struct LNArgs {
-    const bf16_t* x; int ldx;
-    const float* gamma; const float* beta; float eps;
-    bf16_t* y; int ldy;
-    float* mean; float* rstd;
-    int M, C;
-    int patch, H, W;     // patchified output (H, W = spatial dims of the INPUT rows)
-    // backward
-    const bf16_t* dy; int lddy;
-    bf16_t* dx; int lddx;
-    float* dgamma; float* dbeta;
-    const bf16_t* add; int ldadd;    // optional residual-path gradient added to dx (pre-LN transformer blocks)
-    int nt;                          // stream the output past L2 (tensor larger than the Infinity Cache)
-    int y_fp8;                       // y receives OCP e4m3 bytes (ldy in bytes): operand of the fp8 GEMM path
-    int x_f32;                       // x holds fp32 (the text tower keeps its pre-LayerNorm sums in fp32); ldx in elements
-    float* yf; int ldyf;             // optional fp32 copy of y (the text tower's residual stream), forward only
-    const float* res; int ldres;     // optional fp32 residual: the row normalised is x + res, and x is OVERWRITTEN with that sum
-};
 
 // 8 consecutive elements of row m of x (bf16 or fp32 storage) as floats
 __device__ __forceinline__ void ln_load_x8(const LNArgs& a, int m, int c, float* v) {
@@ -375,89 +357,39 @@ __global__ __launch_bounds__(256) void layernorm_bwd_plain_kernel(const LNArgs a
     }
 }
 
-template <bool BWD>
-static int launch_ln(const LNArgs& a, hipStream_t stream) {
-    const int nch = a.C / 8;
-    int G = 8;
-    while (G < nch && G < 64) G <<= 1;
-    int ch = cdiv(nch, G);
-    // round 3, FORWARD only: widths of 3 x 2^k chunks (192, 384, 768, 1536: every ConvNeXt-T / BERT width but 96) take G = 2^k lanes x 3
-    // chunks per row instead of the next power of two with a quarter of the lanes idle: no idle lanes, 64 / G rows and three times the bytes
-    // in flight per wave.  Same-run A/B (tools/ln_ab.py, profiles/r03_ln_ab.txt): forward 498 -> 389 us at M = 1 M x 384 (3.2 -> 4.1 TB/s),
-    // 213 -> 191 at 262 k x 768, 779 -> 745 at 4.2 M x 192; the BACKWARD got slower with it (652 -> 805, 1231 -> 1523, 321 -> 432 us: three
-    // chunks of dgamma / dbeta accumulators and operands per lane) and keeps the round-2 selection.  MMG_LN_CH3=0: off (A/B).
-    // Both knobs are read per call, so that one process can launch either selection (tests/test_layernorm_gpu.py).
-    const char* ch3_env = getenv("MMG_LN_CH3");
-    const int ch3_on = ch3_env ? atoi(ch3_env) : 1;
-    const bool ch3 = !BWD && ch3_on && nch % 3 == 0 && (nch / 3 == 8 || nch / 3 == 16 || nch / 3 == 32 || nch / 3 == 64);
-    if (ch3) { G = nch / 3; ch = 3; }
-    // the image tower's widths on the plain kernels above (MMG_LN_PLAIN=0: off, A/B)
-    const char* plain_env = getenv("MMG_LN_PLAIN");
-    const int plain_on = plain_env ? atoi(plain_env) : 1;
-    const int g3 = nch % 3 == 0 ? nch / 3 : 0;
-    const bool plain = plain_on && (g3 == 4 || g3 == 8 || g3 == 16 || g3 == 32 || g3 == 64) && !a.x_f32 && !a.res && !a.y_fp8 && !a.yf && !a.add &&
-                       (!BWD || (a.mean && a.rstd));
-    if (plain) G = g3;
-    const int rows_per_block = 4 * (64 / G);
-    int blocks = cdiv(a.M, rows_per_block);
-    const int cap = BWD ? 1024 : 4096;
-    if (blocks > cap) blocks = cap;
-    const size_t shm = BWD ? 2 * a.C * sizeof(float) : 0;
-    if (plain) {
-#define LN_PLAIN(GG)                                                                                                      \
-    do {                                                                                                                  \
-        MMG_NOTE_KERNEL(BWD ? "layernorm_bwd_plain_kernel<%d>" : "layernorm_fwd_plain_kernel<%d>", GG);                   \
-        if (BWD) hipLaunchKernelGGL((layernorm_bwd_plain_kernel<GG>), dim3(blocks), dim3(256), shm, stream, a);           \
-        else hipLaunchKernelGGL((layernorm_fwd_plain_kernel<GG>), dim3(blocks), dim3(256), 0, stream, a);                 \
-    } while (0)
-        if (G == 4) LN_PLAIN(4);
-        else if (G == 8) LN_PLAIN(8);
-        else if (G == 16) LN_PLAIN(16);
-        else if (G == 32) LN_PLAIN(32);
-        else LN_PLAIN(64);
-#undef LN_PLAIN
-        return 0;
+// The five LayerNorm doors: validate (layernorm_plan.hip, before any HIP call), plan, launch what the plan names.
+static int ln_run(int door, LNArgs a, hipStream_t stream) {
+    if (ln_check(door, a)) return 1;
+    const LNDoor& d = ln_door(door);
+    const LNPlan p = ln_plan(door, a.M, a.C, a.res != nullptr, a.yf != nullptr, a.add != nullptr, ln_knobs());
+    a.x_f32 = d.x_f32; a.y_fp8 = d.y_fp8; a.nt = p.nt;
+    MMG_NOTE_KERNEL("%s", ln_kernel_name(p.kernel));
+    switch (p.kernel) {
+#define P(OP, G) case LK_##OP##_plain_##G: hipLaunchKernelGGL((layernorm_##OP##_plain_kernel<G>), dim3(p.blocks), dim3(p.block), p.lds, stream, a); break;
+#define X(OP, G, CH) case LK_##OP##_##G##_##CH: hipLaunchKernelGGL((layernorm_##OP##_kernel<G, CH>), dim3(p.blocks), dim3(p.block), p.lds, stream, a); break;
+        LN_KERNELS(P, X)
+#undef P
+#undef X
+        default: mmg_set_error("%s: no kernel for plan %d", d.name, p.kernel); return 1;
     }
-#define LN_LAUNCH(GG, CC)                                                                                       \
-    do {                                                                                                        \
-        MMG_NOTE_KERNEL(BWD ? "layernorm_bwd_kernel<%d, %d>" : "layernorm_fwd_kernel<%d, %d>", GG, CC);         \
-        if (BWD) hipLaunchKernelGGL((layernorm_bwd_kernel<GG, CC>), dim3(blocks), dim3(256), shm, stream, a);  \
-        else hipLaunchKernelGGL((layernorm_fwd_kernel<GG, CC>), dim3(blocks), dim3(256), 0, stream, a);        \
-    } while (0)
-    if (ch3 && G == 8) LN_LAUNCH(8, 3);
-    else if (ch3 && G == 16) LN_LAUNCH(16, 3);
-    else if (ch3 && G == 32) LN_LAUNCH(32, 3);
-    else if (ch3) LN_LAUNCH(64, 3);
-    else if (G == 8) LN_LAUNCH(8, 1);
-    else if (G == 16) LN_LAUNCH(16, 1);
-    else if (G == 32) LN_LAUNCH(32, 1);
-    else if (ch <= 1) LN_LAUNCH(64, 1);
-    else if (ch <= 2) LN_LAUNCH(64, 2);
-    else if (ch <= 4) LN_LAUNCH(64, 4);
-    else if (ch <= 8) LN_LAUNCH(64, 8);
-    else { mmg_set_error("layernorm: C=%d too wide (max 4096)", a.C); return 1; }
-#undef LN_LAUNCH
+    MMG_LAUNCH_CHECK(d.name);
     return 0;
 }
 
-static int ln_check(const char* who, int M, int C, int patch, int H, int W) {
-    MMG_CHECK_ARG(M > 0 && C >= 8 && C % 8 == 0 && C <= 4096, "%s: M=%d C=%d (C must be a multiple of 8, <= 4096)", who, M, C);
-    MMG_CHECK_ARG(!patch || (H > 1 && W > 1 && M % (H * W) == 0), "%s: patchified layout needs H=%d W=%d dividing M=%d", who, H, W, M);
-    return 0;
+// the operands all three forward doors take (x: bf16 or fp32 rows; y: bf16 or e4m3 bytes)
+static LNArgs ln_fwd_args(const void* x, int ldx, const float* gamma, const float* beta, float eps, void* y, int ldy, float* mean, float* rstd,
+                          int M, int C) {
+    LNArgs a = {};
+    a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.y = (bf16_t*)y; a.ldy = ldy;
+    a.mean = mean; a.rstd = rstd; a.M = M; a.C = C;
+    return a;
 }
 
 MMG_API int mmg_layernorm_fwd(const void* x, int ldx, const float* gamma, const float* beta, float eps, void* y, int ldy,
                               float* mean, float* rstd, int M, int C, int patch, int H, int W, hipStream_t stream) {
-    if (ln_check("mmg_layernorm_fwd", M, C, patch, H, W)) return 1;
-    MMG_CHECK_ARG(x && gamma && beta && y && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= (patch ? 4 * C : C),
-                  "mmg_layernorm_fwd: bad pointer or leading dimension");
-    LNArgs a = {};
-    a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.y = (bf16_t*)y; a.ldy = ldy;
-    a.mean = mean; a.rstd = rstd; a.M = M; a.C = C; a.patch = patch; a.H = H; a.W = W;
-    a.nt = (size_t)M * C * 2 >= ((size_t)256 << 20);
-    if (launch_ln<false>(a, stream)) return 1;
-    MMG_LAUNCH_CHECK("mmg_layernorm_fwd");
-    return 0;
+    LNArgs a = ln_fwd_args(x, ldx, gamma, beta, eps, y, ldy, mean, rstd, M, C);
+    a.patch = patch; a.H = H; a.W = W;
+    return ln_run(LN_FWD, a, stream);
 }
 
 // LayerNorm of an fp32 input row (the text tower's pre-LayerNorm sums x + f(x) stay in fp32: bf16 rounding of the residual
@@ -466,65 +398,40 @@ MMG_API int mmg_layernorm_fwd(const void* x, int ldx, const float* gamma, const 
 // and its epilogue stays untouched (a runtime fp32-residual branch there cost the big ConvNeXt GEMMs 4-6 %).
 MMG_API int mmg_layernorm_fwd_f32(float* x, int ldx, const float* res, int ldres, const float* gamma, const float* beta, float eps,
                                   void* y, int ldy, float* yf, int ldyf, float* mean, float* rstd, int M, int C, hipStream_t stream) {
-    if (ln_check("mmg_layernorm_fwd_f32", M, C, 0, 0, 0)) return 1;
-    MMG_CHECK_ARG(x && gamma && beta && y && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= C && (!yf || (ldyf >= C && ldyf % 4 == 0)) &&
-                      (!res || (ldres >= C && ldres % 4 == 0)), "mmg_layernorm_fwd_f32: bad pointer or leading dimension");
-    LNArgs a = {};
-    a.x = reinterpret_cast<const bf16_t*>(x); a.x_f32 = 1; a.ldx = ldx; a.res = res; a.ldres = ldres; a.gamma = gamma; a.beta = beta; a.eps = eps;
-    a.y = (bf16_t*)y; a.ldy = ldy; a.yf = yf; a.ldyf = ldyf; a.mean = mean; a.rstd = rstd; a.M = M; a.C = C;
-    if (launch_ln<false>(a, stream)) return 1;
-    MMG_LAUNCH_CHECK("mmg_layernorm_fwd_f32");
-    return 0;
-}
-MMG_API int mmg_layernorm_bwd_f32(const void* dy, int lddy, const float* x, int ldx, const float* mean, const float* rstd,
-                                  const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C,
-                                  const void* add, int ldadd, hipStream_t stream) {
-    if (ln_check("mmg_layernorm_bwd_f32", M, C, 0, 0, 0)) return 1;
-    MMG_CHECK_ARG(dy && x && mean && rstd && gamma && dx && ((dgamma == nullptr) == (dbeta == nullptr)) && ldx % 8 == 0 &&
-                      lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C && lddx >= C && (!add || (ldadd >= C && ldadd % 8 == 0)),
-                  "mmg_layernorm_bwd_f32: bad pointer or leading dimension");
-    LNArgs a = {};
-    a.x = reinterpret_cast<const bf16_t*>(x); a.x_f32 = 1; a.ldx = ldx; a.gamma = gamma;
-    a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.M = M; a.C = C;
-    a.dy = (const bf16_t*)dy; a.lddy = lddy; a.dx = (bf16_t*)dx; a.lddx = lddx; a.dgamma = dgamma; a.dbeta = dbeta;
-    a.add = (const bf16_t*)add; a.ldadd = ldadd;
-    if (launch_ln<true>(a, stream)) return 1;
-    MMG_LAUNCH_CHECK("mmg_layernorm_bwd_f32");
-    return 0;
+    LNArgs a = ln_fwd_args(x, ldx, gamma, beta, eps, y, ldy, mean, rstd, M, C);
+    a.res = res; a.ldres = ldres; a.yf = yf; a.ldyf = ldyf;
+    return ln_run(LN_FWD_F32, a, stream);
 }
 
 // LayerNorm whose output is written as e4m3 bytes (unscaled, saturating): the A operand of mmg_gemm_nt_fp8
 MMG_API int mmg_layernorm_fwd_fp8(const void* x, int ldx, const float* gamma, const float* beta, float eps, void* y8, int ldy,
                                   float* mean, float* rstd, int M, int C, hipStream_t stream) {
-    if (ln_check("mmg_layernorm_fwd_fp8", M, C, 0, 0, 0)) return 1;
-    MMG_CHECK_ARG(x && gamma && beta && y8 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= C,
-                  "mmg_layernorm_fwd_fp8: bad pointer or leading dimension");
+    return ln_run(LN_FWD_FP8, ln_fwd_args(x, ldx, gamma, beta, eps, y8, ldy, mean, rstd, M, C), stream);
+}
+
+// the operands both backward doors take (x: bf16 or fp32 rows)
+static LNArgs ln_bwd_args(const void* dy, int lddy, const void* x, int ldx, const float* mean, const float* rstd, const float* gamma,
+                          void* dx, int lddx, float* dgamma, float* dbeta, int M, int C, const void* add, int ldadd) {
     LNArgs a = {};
-    a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.y = (bf16_t*)y8; a.ldy = ldy;
-    a.mean = mean; a.rstd = rstd; a.M = M; a.C = C; a.y_fp8 = 1;
-    if (launch_ln<false>(a, stream)) return 1;
-    MMG_LAUNCH_CHECK("mmg_layernorm_fwd_fp8");
-    return 0;
+    a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);
+    a.M = M; a.C = C;
+    a.dy = (const bf16_t*)dy; a.lddy = lddy; a.dx = (bf16_t*)dx; a.lddx = lddx; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.add = (const bf16_t*)add; a.ldadd = ldadd;
+    return a;
 }
 
 MMG_API int mmg_layernorm_bwd(const void* dy, int lddy, const void* x, int ldx, const float* mean, const float* rstd,
                               const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C,
                               int patch, int H, int W, const void* add, int ldadd, hipStream_t stream) {
-    if (ln_check("mmg_layernorm_bwd", M, C, patch, H, W)) return 1;
-    // odd H / W: dy is [(M / (H W)) (H/2) (W/2), 4C] as the forward wrote it; the dropped pixels get dx = 0 (+ add) and no dy address is formed
-    MMG_CHECK_ARG(dy && x && mean && rstd && gamma && dx && ((dgamma == nullptr) == (dbeta == nullptr)) &&
-                      ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C && lddx >= C && lddy >= (patch ? 4 * C : C),
-                  "mmg_layernorm_bwd: bad pointer or leading dimension");
-    LNArgs a = {};
-    a.x = (const bf16_t*)x; a.ldx = ldx; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);
-    a.M = M; a.C = C; a.patch = patch; a.H = H; a.W = W;
-    a.dy = (const bf16_t*)dy; a.lddy = lddy; a.dx = (bf16_t*)dx; a.lddx = lddx; a.dgamma = dgamma; a.dbeta = dbeta;
-    a.add = (const bf16_t*)add; a.ldadd = ldadd;
-    a.nt = (size_t)M * C * 2 >= ((size_t)256 << 20);
-    MMG_CHECK_ARG(!add || (ldadd >= C && ldadd % 8 == 0), "mmg_layernorm_bwd: bad ldadd=%d", ldadd);
-    if (launch_ln<true>(a, stream)) return 1;
-    MMG_LAUNCH_CHECK("mmg_layernorm_bwd");
-    return 0;
+    LNArgs a = ln_bwd_args(dy, lddy, x, ldx, mean, rstd, gamma, dx, lddx, dgamma, dbeta, M, C, add, ldadd);
+    a.patch = patch; a.H = H; a.W = W;
+    return ln_run(LN_BWD, a, stream);
+}
+
+MMG_API int mmg_layernorm_bwd_f32(const void* dy, int lddy, const float* x, int ldx, const float* mean, const float* rstd,
+                                  const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta, int M, int C,
+                                  const void* add, int ldadd, hipStream_t stream) {
+    return ln_run(LN_BWD_F32, ln_bwd_args(dy, lddy, x, ldx, mean, rstd, gamma, dx, lddx, dgamma, dbeta, M, C, add, ldadd), stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,10 +1,11 @@
 """Float64 reference, exact-data regime, derived error bars and an emulation (with mutations) for the LayerNorm kernels of
 csrc/norm_elementwise.hip: mmg_layernorm_fwd, mmg_layernorm_fwd_f32, mmg_layernorm_fwd_fp8, mmg_layernorm_bwd, mmg_layernorm_bwd_f32
-(four kernel templates, 28 instantiations behind launch_ln).
+(four kernel templates, the 28 instantiations of the kernel table in csrc/layernorm_plan.h, chosen by ln_plan).
 
 Imported by tests/test_layernorm_ref_cpu.py (no GPU: the table names every instantiation and mode, the exactness preconditions hold on
-the reference alone, the emulation is inside every bar and every mutation of it leaves them) and by tests/test_layernorm_gpu.py (the
-kernels against the same reference).  Everything here runs on the CPU.
+the reference alone, the emulation is inside every bar and every mutation of it leaves them), by tests/test_layernorm_plan_cpu.py (no
+GPU: the library's own plans against select / plan below and against the launches recorded before the plan existed) and by
+tests/test_layernorm_gpu.py (the kernels against the same reference).  Everything here runs on the CPU.
 
 The operation (xs = the row normalised: x, or fp32(x + res), which the fp32-row forward also writes back over x):
     forward   mean, var = row statistics of xs;  rstd = (var + eps)^-1/2;  xhat = (xs - mean) rstd;  y = xhat gamma + beta
@@ -131,8 +132,16 @@ class Case(NamedTuple):
             return "mmg_layernorm_fwd_fp8" if self.fp8 else "mmg_layernorm_fwd_f32" if self.x32 else "mmg_layernorm_fwd"
         return "mmg_layernorm_bwd_f32" if self.x32 else "mmg_layernorm_bwd"
 
+    @property
+    def plan_args(self):
+        """The case as mmg_layernorm_plan takes it: (door, M, C, res, yf, add)."""
+        return (DOORS.index(self.entry), self.M, self.C, int(self.res), int(self.yf), int(self.add))
 
-# ---- launch_ln's selection, restated ---------------------------------------------------------------------------------------------
+
+DOORS = ("mmg_layernorm_fwd", "mmg_layernorm_fwd_f32", "mmg_layernorm_fwd_fp8", "mmg_layernorm_bwd", "mmg_layernorm_bwd_f32")
+
+
+# ---- ln_plan's selection (csrc/layernorm_plan.hip), restated: independent of it, never through mmg_layernorm_plan ------------------
 def select(case):
     """-> (template: 'plain' | 'generic', G lanes per row, CH chunks per lane)."""
     nch = case.C // 8

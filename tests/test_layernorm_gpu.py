@@ -3,12 +3,13 @@ mmg_layernorm_fwd_fp8, mmg_layernorm_bwd and mmg_layernorm_bwd_f32) against the 
 tests/test_layernorm_ref_cpu.py shows on the CPU that the table reaches every instantiation and call mode, that torch.equal is justified
 where it is used and that subtly wrong arithmetic leaves every bar.
 
-Every case of layernorm_ref.CASES sets MMG_LN_PLAIN / MMG_LN_CH3 through the environment (the launcher reads them per call) and runs ONE
+Every case of layernorm_ref.CASES sets MMG_LN_PLAIN / MMG_LN_CH3 through the environment (ln_knobs reads them per call) and runs ONE
 launch through mmgclip._hip.call on buffers of the test's own: every output - mean and rstd too - is pre-filled with NaN bits and
 carries sentinel rows past the last row the kernel owns (patchified outputs: past row n (H/2) (W/2)) and, where its leading dimension is
 wider than its row, sentinel columns; strided inputs carry NaN in the columns no kernel may read.  Integer cases: torch.equal against
 the reference cast to the output type for the outputs layernorm_ref lists as exact.  Everything else: the derived bars; every figure
-goes to `measured`.  Beside the numbers: the launch is the instantiation the table names (mmg_last_kernel), no owned element holds a NaN
+goes to `measured`.  Beside the numbers: the launch is the instantiation the table names and the one mmg_layernorm_plan names for the
+same call (mmg_last_kernel; the plan itself is pinned on the CPU, tests/test_layernorm_plan_cpu.py), no owned element holds a NaN
 fill, every sentinel is intact, rows that are equal (the rows have period P) give equal bits - the large cases (grid-stride loop,
 non-temporal stores) are compared on the device against the P reference rows gathered by row % P -, dgamma / dbeta start from a non-zero
 pre-fill, y = bf16(yf) and x_after = fp32(x + res) bit for bit.
@@ -21,6 +22,7 @@ import ctypes
 import pytest
 import torch
 
+from mmgclip import _hip
 from tests import layernorm_ref as R
 from tests.conftest import measured
 
@@ -101,7 +103,6 @@ def _f32(t, dev):
 
 def _launch(case, d, dev):
     """The case's launch -> ({output: Buf}, {accumulated output: device tensor}, kernel noted, the call's arguments kept alive)."""
-    from mmgclip import _hip
     call, ptr, stream = _hip.call, _hip.ptr, _hip.stream
     C, M = case.C, case.M
     n = R.base_rows(case)
@@ -229,6 +230,9 @@ def test_kernels_against_float64(case, dev, monkeypatch):
                        + f" ({vals[k + '_differ']:.5f} of the elements differ from the reference cast to the output type)")
     if name != R.kernel_note(case):
         bad.append(f"launched {name!r}, the table says {R.kernel_note(case)!r}")
+    planned = _hip.load().mmg_layernorm_plan(*case.plan_args).decode().split(" grid=")[0]     # (monkeypatch still holds the case's knobs)
+    if name != planned:
+        bad.append(f"launched {name!r}, mmg_layernorm_plan names {planned!r}")
     assert not bad, bad
 
 
@@ -271,13 +275,13 @@ def test_row_outputs_give_the_same_bits_run_to_run(case, dev, monkeypatch):
 REJECTED = {
     "C=4104": dict(C=4104), "C=12": dict(C=12), "ldx=C+4": dict(ldx=260), "patch, M % (H W) != 0": dict(patch=1, H=3, W=5, ldy=1024, lddy=1024),
     "ldy < 4C with patch": dict(patch=1, H=4, W=4, ldy=512, lddy=512), "dgamma without dbeta": dict(no_dbeta=True),
+    "lddy < C": dict(lddy=128),
 }
 
 
 @pytest.mark.parametrize("what", list(REJECTED))
 def test_bad_arguments_are_rejected_and_nothing_is_launched(what, dev):
     """An error string comes back, no kernel is noted and the outputs keep their fill."""
-    from mmgclip import _hip
     lib, ptr = _hip.load(), _hip.ptr
     kw = dict(C=256, M=16, ldx=None, ldy=None, lddy=None, patch=0, H=0, W=0, no_dbeta=False)
     kw.update(REJECTED[what])
@@ -300,7 +304,7 @@ def test_bad_arguments_are_rejected_and_nothing_is_launched(what, dev):
         before = lib.mmg_last_kernel()
         calls = {}
         fwd_only = what == "ldy < 4C with patch"
-        bwd_only = what == "dgamma without dbeta"
+        bwd_only = what in ("dgamma without dbeta", "lddy < C")
         if not bwd_only:
             calls["mmg_layernorm_fwd"] = lambda: lib.mmg_layernorm_fwd(ptr(x), ldx, ptr(gamma), ptr(beta), eps, ptr(y.t), ldy, ptr(mean.t),
                                                                        ptr(rstd.t), M, C, kw["patch"], kw["H"], kw["W"], s)

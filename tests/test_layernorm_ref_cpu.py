@@ -1,8 +1,9 @@
-"""tests/layernorm_ref.py without a GPU: the table reaches every instantiation launch_ln can launch and every call mode, the kernel
+"""tests/layernorm_ref.py without a GPU: the table reaches every instantiation of the kernel table (csrc/layernorm_plan.h) and every call mode, the kernel
 notes are spelt as the launcher spells them, torch.equal is justified where the table uses it (on the reference alone), the fp8
 boundary share is within its cap, the emulation of the kernels' arithmetic is inside every bar on every case (exact where the table says
 exact), and each subtly wrong variant of it leaves the bars on every case that contains the feature it breaks.  (That the restated
-selection agrees with launch_ln itself is checked on the device: tests/test_layernorm_gpu.py compares the kernel note of every case.)"""
+selection agrees with the library's ln_plan is checked in tests/test_layernorm_plan_cpu.py, without a GPU; tests/test_layernorm_gpu.py
+compares the kernel note of every launch with both.)"""
 import pytest
 import torch
 
