@@ -341,6 +341,25 @@ int mmg_cnblock_bwdw(const void* dy, const void* xd, const float* ln_w, const fl
                      const float* b1f, void* dd, float* dW1, float* db1, float* dW2raw, float* db2raw, float* ln_dw,
                      float* ln_db, long long M, int C, mmg_stream_t stream);
 
+/* ConvNeXt stem (features[0]: Conv2d(Cin, C, 4, 4) as a GEMM over mmg_patchify's rows, then LayerNorm2d) in two launches
+ * (csrc/stem.hip); the [M,C] tensors s0 = p0 w^T + bias and ds0 that the three-launch path (mmg_gemm_nt, mmg_layernorm_fwd;
+ * mmg_layernorm_bwd, mmg_gemm_tn_acc) stores between its kernels never reach memory.  mmg_stem_supported(C, kp): C in {96, 128} and
+ * kp in {32, 64}; any M >= 1 (rows are addressed with 64-bit offsets: no 4 GiB range to split a launch at).
+ * p0: bf16 [M,kp]; w: bf16 [C,kp] (the working copy of the conv weight, zero-padded to kp); bias, ln_w, ln_b: fp32 [C].
+ * mmg_stem_fwd: x (bf16 [M,C]) = LN(bf16(p0 w^T + bias)) - the product accumulates in fp32 and is rounded to bf16 BEFORE the
+ * LayerNorm, as the stored s0 was; mean / rstd (fp32 [M]): the row statistics of that rounded s0, both NULL for a pass that saves nothing.
+ * mmg_stem_bwd: recomputes s0 (rounded to bf16) from p0, forms xhat from the saved statistics, runs the LayerNorm backward in registers,
+ * rounds ds0 to bf16 as the stored tensor was, and ACCUMULATES (fp32 atomics, once per workgroup) dW [C,kp] += ds0^T p0,
+ * db [C] += colsum(ds0), ln_dw [C] += sum dx xhat, ln_db [C] += colsum(dx).  Nothing [M,C]-wide is written.
+ * Replaces autograd of torchvision ConvNeXt features[0] (the reference runs the tower frozen, mmgclip/networks/encoder.py:53).
+ * Additive entry points: mmg_abi_version() stays 5. */
+int mmg_stem_supported(int C, int kp);
+int mmg_stem_fwd(const void* p0, const void* w, const float* bias, const float* ln_w, const float* ln_b, float eps, void* x,
+                 float* mean, float* rstd, long long M, int C, int kp, mmg_stream_t stream);
+int mmg_stem_bwd(const void* dx, const void* p0, const void* w, const float* bias, const float* ln_w, const float* mean,
+                 const float* rstd, float* dW, float* db, float* ln_dw, float* ln_db, long long M, int C, int kp,
+                 mmg_stream_t stream);
+
 /* ---- AveragedMedicalCLIPLoss helpers (reference mmgclip/loss/losses.py:98-216) ------------------------------------------------ */
 
 /* `_assign_labels` (losses.py:148-162) on the device: walking i = 0..n-1, an unlabelled text opens the next cluster and every

@@ -251,6 +251,48 @@ def patchify(img, P, Kp, scale16, geom=None, tone=None):
     return out
 
 
+def stem_supported(C, kp):
+    """Fused stem launches (csrc/stem.hip): C in {96, 128}, kp in {32, 64}."""
+    return bool(_hip.load().mmg_stem_supported(int(C), int(kp)))
+
+
+def stem_fused_enabled():
+    """MMG_STEM_FUSED (read per call, like MMG_BWDW_VAR: one process can A/B the two paths): 0 = the three-launch stem."""
+    return os.environ.get("MMG_STEM_FUSED", "1") != "0"
+
+
+def stem_fwd(p0, w, bias, ln_w, ln_b, eps, want_stats=True):
+    """p0 bf16 [M,kp] (patchify's rows), w bf16 [C,kp] -> x = LN(bf16(p0 w^T + bias)) bf16 [M,C], mean, rstd (fp32 [M], or None, None)."""
+    M, kp = p0.shape
+    C = w.shape[0]
+    assert p0.dtype == BF16 and w.dtype == BF16 and p0.is_contiguous() and w.is_contiguous() and w.shape[1] == kp
+    _hip.require_gpu(p0, w, bias, ln_w, ln_b)
+    x = torch.empty(M, C, device=p0.device, dtype=BF16)
+    mean = torch.empty(M, device=p0.device, dtype=torch.float32) if want_stats else None
+    rstd = torch.empty(M, device=p0.device, dtype=torch.float32) if want_stats else None
+    # algorithmic work: the product; p0 read once, x (+ the statistics) written once
+    PROFILE.timed("stem_fwd_kernel", 2.0 * M * C * kp, 2 * M * (kp + C) + (8 * M if want_stats else 0) + 2 * C * kp,
+                  lambda: call("mmg_stem_fwd", ptr(p0), ptr(w), ptr(bias), ptr(ln_w), ptr(ln_b), float(eps), ptr(x), ptr(mean), ptr(rstd),
+                               M, C, kp, stream()), f"M={M} C={C} kp={kp}" + (" +stats" if want_stats else ""))
+    return x, mean, rstd
+
+
+def stem_bwd(dx, p0, w, bias, ln_w, mean, rstd, dW, db, ln_dw, ln_db):
+    """Accumulates dW fp32 [C,kp] += ds0^T p0, db += colsum(ds0), ln_dw, ln_db (fp32 [C]) from dx bf16 [M,C], p0 and the forward's
+    statistics; ds0 = LayerNorm backward at the recomputed s0, rounded to bf16.  Writes nothing [M,C]-wide."""
+    M, kp = p0.shape
+    C = w.shape[0]
+    assert dx.dtype == BF16 and p0.dtype == BF16 and dx.is_contiguous() and p0.is_contiguous() and tuple(dx.shape) == (M, C)
+    assert mean.dtype == rstd.dtype == torch.float32 and mean.numel() == rstd.numel() == M
+    for t, n in ((dW, C * kp), (db, C), (ln_dw, C), (ln_db, C)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    _hip.require_gpu(dx, p0, w, bias, ln_w, mean, rstd, dW, db, ln_dw, ln_db)
+    # algorithmic work: the recomputed product is overhead, dW = ds0^T p0 is counted; dx, p0 and the statistics read once
+    PROFILE.timed("stem_bwd_kernel", 2.0 * M * C * kp, 2 * M * (kp + C) + 8 * M + 6 * C * kp,
+                  lambda: call("mmg_stem_bwd", ptr(dx), ptr(p0), ptr(w), ptr(bias), ptr(ln_w), ptr(mean), ptr(rstd), ptr(dW), ptr(db),
+                               ptr(ln_dw), ptr(ln_db), M, C, kp, stream()), f"M={M} C={C} kp={kp}")
+
+
 def adamw_step(p, g, m, v, p16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     call("mmg_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(beta1), float(beta2),
          float(eps), float(wd), int(step), float(grad_scale), stream())

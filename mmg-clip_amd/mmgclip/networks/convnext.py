@@ -290,8 +290,14 @@ class ConvNextTower(Tower):
             saved["sd"] = (steps, table)
         b = 0
         p0 = K.patchify(img, 4, self.kp, self.scale16, *(tabs or (None, None)))
-        s0 = L.gemm_nt(p0, wc["stem.w"], bias=f[0][0].bias.data)
-        x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
+        if K.stem_fused_enabled() and K.stem_supported(self.dims[0], self.kp):
+            # conv GEMM + LayerNorm in one launch (csrc/stem.hip): s0 = p0 w^T + bias is rounded to bf16 on chip and never stored;
+            # the record's None tells the backward to recompute it from p0
+            s0 = None
+            x, mean, rstd = K.stem_fwd(p0, wc["stem.w"], f[0][0].bias.data, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
+        else:                                       # three launches (MMG_STEM_FUSED=0, or a width the fused kernels do not have)
+            s0 = L.gemm_nt(p0, wc["stem.w"], bias=f[0][0].bias.data)
+            x, mean, rstd = K.layernorm_fwd(s0, f[0][1].weight.data, f[0][1].bias.data, LN_EPS, want_stats=save)
         if save:
             saved["stem"] = (p0, s0, mean, rstd)
         for si, p in enumerate(plan):
@@ -439,8 +445,12 @@ class ConvNextTower(Tower):
                 if announce:
                     A.mark_ready((f"features.{1 + 2 * si}.",) + ((f"features.{2 + 2 * si}.",) if si < 3 else ()))
         p0, s0, mean, rstd = saved["stem"]
-        ds0 = K.layernorm_bwd(dx, s0, mean, rstd, f[0][1].weight.data, self._g(f[0][1], "weight"), self._g(f[0][1], "bias"))
-        L.gemm_tn_acc(ds0, p0, tmp["stem.dw"], colsum=self._g(f[0][0], "bias"))
+        if s0 is None:                      # the forward took the fused launch: LayerNorm backward + both weight gradients in one, nothing [M,C] written
+            K.stem_bwd(dx, p0, wc["stem.w"], f[0][0].bias.data, f[0][1].weight.data, mean, rstd, tmp["stem.dw"], self._g(f[0][0], "bias"),
+                       self._g(f[0][1], "weight"), self._g(f[0][1], "bias"))
+        else:
+            ds0 = K.layernorm_bwd(dx, s0, mean, rstd, f[0][1].weight.data, self._g(f[0][1], "weight"), self._g(f[0][1], "bias"))
+            L.gemm_tn_acc(ds0, p0, tmp["stem.dw"], colsum=self._g(f[0][0], "bias"))
         if final:                           # fold the GEMM-shaped stem temporary ([C0, kp], zero-padded tail) into the torch-layout gradient
             fold_conv_grad(tmp["stem.dw"], self._g(f[0][0], "weight"), self.dims[0], self.in_chans, 4, 4)
 
