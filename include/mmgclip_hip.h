@@ -360,6 +360,21 @@ int mmg_stem_bwd(const void* dx, const void* p0, const void* w, const float* bia
                  const float* rstd, float* dW, float* db, float* ln_dw, float* ln_db, long long M, int C, int kp,
                  mmg_stream_t stream);
 
+/* Data-gradient GEMM with the LayerNorm backward in its epilogue (csrc/gemm_lnbwd.hip): the two launches mmg_gemm_nt_bf16 (dln = A B^T,
+ * bf16) + mmg_layernorm_bwd (dln, x -> dx) in one, with their roundings; dln is never stored.  A: bf16 [M,K], B: bf16 [N,K];
+ * dln = bf16(A B^T) (fp32 accumulation); per pixel (C consecutive columns of a row): xhat = (x - mean) rstd, g = dln gamma,
+ * dx = bf16(rstd (g - mean_C(g) - xhat mean_C(g xhat))); dgamma [C] += sum dln xhat, dbeta [C] += sum dln (fp32 atomics, once per
+ * workgroup; both may be NULL).  patch = 0: N == C, GEMM row r is LayerNorm row r.  patch = 1: N == 4 C, row r = (n, ph, pw) and its
+ * segment s are pixel (n, 2 ph + s / 2, 2 pw + s % 2) of an H x W map; x, dx (bf16 [pixels, C]), mean, rstd (fp32 [pixels]) by pixel.
+ * mmg_gemm_nt_lnbwd_supported: N % 384 == 0, K % 64 == 0, K >= 64, C in {96, 192, 384}, N == C (patch 0) or 4 C (patch 1), and for
+ * patch 1 even H and W (odd maps keep the two launches).  The launch also needs M >= 1 and, for patch 1, M a multiple of (H/2)(W/2).
+ * Everything is validated before any HIP call; an unsupported shape returns non-zero and launches nothing.
+ * Additive entry points: mmg_abi_version() stays 5. */
+int mmg_gemm_nt_lnbwd_supported(int N, int K, int C, int patch, int H, int W);
+int mmg_gemm_nt_lnbwd(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const void* x, int ldx,
+                      const float* mean, const float* rstd, const float* gamma, void* dx, int lddx, float* dgamma, float* dbeta,
+                      int C, int patch, int H, int W, mmg_stream_t stream);
+
 /* ---- AveragedMedicalCLIPLoss helpers (reference mmgclip/loss/losses.py:98-216) ------------------------------------------------ */
 
 /* `_assign_labels` (losses.py:148-162) on the device: walking i = 0..n-1, an unlabelled text opens the next cluster and every

@@ -293,6 +293,39 @@ def stem_bwd(dx, p0, w, bias, ln_w, mean, rstd, dW, db, ln_dw, ln_db):
                                ptr(ln_dw), ptr(ln_db), M, C, kp, stream()), f"M={M} C={C} kp={kp}")
 
 
+def gemm_nt_lnbwd_supported(N, K, C, patch_hw=None):
+    """The data-gradient GEMM with the LayerNorm backward in its epilogue (csrc/gemm_lnbwd.hip): N % 384 == 0, K % 64 == 0, C in
+    {96, 192, 384}, N == C (plain rows) or 4 C with an even H x W map (patch_hw)."""
+    patch, H, W = (0, 0, 0) if patch_hw is None else (1, int(patch_hw[0]), int(patch_hw[1]))
+    return bool(_hip.load().mmg_gemm_nt_lnbwd_supported(int(N), int(K), int(C), patch, H, W))
+
+
+def lnbwd_fused_enabled():
+    """MMG_LNBWD_FUSED (read per call, like MMG_STEM_FUSED): 0 = GEMM and LayerNorm backward in two launches everywhere."""
+    return os.environ.get("MMG_LNBWD_FUSED", "1") != "0"
+
+
+def gemm_nt_lnbwd(a, b, x, mean, rstd, gamma, dgamma=None, dbeta=None, patch_hw=None, out=None):
+    """dx = LayerNorm backward of dln = bf16(a[M,K] b[N,K]^T) at x (bf16 [pixels, C]) and its saved statistics, in one launch; dln is
+    never stored.  patch_hw = (H, W): a row of dln holds the four pixels of a 2 x 2 patch (N = 4 C), as layernorm_bwd(patch_hw=) reads it.
+    dgamma / dbeta (fp32 [C]) are accumulated into."""
+    M, Kd = a.shape
+    N = b.shape[0]
+    P, C = x.shape
+    patch, H, W = (0, 0, 0) if patch_hw is None else (1, int(patch_hw[0]), int(patch_hw[1]))
+    assert a.dtype == BF16 and b.dtype == BF16 and x.dtype == BF16 and b.shape[1] == Kd
+    assert P == (4 * M if patch else M) and mean.numel() == rstd.numel() == P and mean.dtype == rstd.dtype == torch.float32
+    assert a.stride(1) == 1 and b.stride(1) == 1 and x.stride(1) == 1
+    _hip.require_gpu(a, b, x, mean, rstd, gamma, dgamma, dbeta, out)
+    dx = out if out is not None else torch.empty(P, C, device=x.device, dtype=BF16)
+    # algorithmic work: the product; both operands read once, x read and dx written once (4 M N bytes), the statistics and gamma
+    PROFILE.timed("gemm_nt_lnbwd_kernel", 2.0 * M * N * Kd, 2 * M * Kd + 2 * N * Kd + 4 * M * N + 8 * P + 12 * C,
+                  lambda: call("mmg_gemm_nt_lnbwd", ptr(a), a.stride(0), ptr(b), b.stride(0), M, N, Kd, ptr(x), x.stride(0), ptr(mean),
+                               ptr(rstd), ptr(gamma), ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta), C, patch, H, W, stream()),
+                  f"M={M} N={N} K={Kd} C={C}" + (" patchified" if patch else ""))
+    return dx
+
+
 def adamw_step(p, g, m, v, p16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     call("mmg_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(beta1), float(beta2),
          float(eps), float(wd), int(step), float(grad_scale), stream())

@@ -54,6 +54,12 @@ def _fused_save_maxc():
     return int(os.environ.get("MMG_MLP_FUSED_SAVE_MAXC", "384"))
 
 
+def lnbwd_fused(M, N, Kd, C, patch_hw=None):
+    """Whether the data-gradient GEMM [M,Kd] x [N,Kd]^T in front of a LayerNorm backward of width C takes the one-launch form
+    (csrc/gemm_lnbwd.hip): MMG_LNBWD_FUSED != 0 (read per call) and a shape the kernel has."""
+    return K.lnbwd_fused_enabled() and K.gemm_nt_lnbwd_supported(N, Kd, C, patch_hw)
+
+
 class LayerNorm2d(nn.LayerNorm):
     """Parameter container with torchvision's name; the arithmetic runs in mmg_layernorm_fwd."""
 
@@ -392,7 +398,13 @@ class ConvNextTower(Tower):
             K.layernorm_fwd(rec.d, blk.block[2].weight.data, blk.block[2].bias.data, LN_EPS, want_stats=False)[0]
         L.gemm_tn_acc(dh, ln, self._g(blk.block[3], "weight"), colsum=self._g(blk.block[3], "bias"))
         del ln
-        dln = L.gemm_nt(dh, wc[key + ".w1t"])
+        w1t, lnm = wc[key + ".w1t"], blk.block[2]
+        if lnbwd_fused(dh.shape[0], w1t.shape[0], w1t.shape[1], rec.d.shape[1]):
+            # dln = dh W1 never reaches memory: the LayerNorm backward rides in the GEMM's epilogue (csrc/gemm_lnbwd.hip)
+            dd = K.gemm_nt_lnbwd(dh, w1t, rec.d, rec.mean, rec.rstd, lnm.weight.data, self._g(lnm, "weight"), self._g(lnm, "bias"))
+            del dh
+            return dd
+        dln = L.gemm_nt(dh, w1t)
         del dh
         return self._ln_bwd(dln, rec.d, rec.mean, rec.rstd, blk)
 
@@ -414,11 +426,17 @@ class ConvNextTower(Tower):
                 x, mean, rstd, ld = saved[f"ds{si}"]
                 conv, lnm = f[2 + 2 * si][1], f[2 + 2 * si][0]
                 L.gemm_tn_acc(dx, ld, tmp[f"ds{si}.dw"], colsum=self._g(conv, "bias"))
-                dld = L.gemm_nt(dx, wc[f"ds{si}.wt"])
+                wt = wc[f"ds{si}.wt"]
                 h, w_ = maps[si]                   # (odd sizes: the dropped last row / column gets a zero gradient here)
-                dx = K.layernorm_bwd(dld, x, mean, rstd, lnm.weight.data, self._g(lnm, "weight"), self._g(lnm, "bias"),
-                                     patch_hw=(h, w_))
-                del dld
+                if lnbwd_fused(dx.shape[0], wt.shape[0], wt.shape[1], C, (h, w_)):
+                    # even maps: dld = dx Wt stays on chip, one launch (odd maps need dx = 0 in pixels no GEMM row visits)
+                    dx = K.gemm_nt_lnbwd(dx, wt, x, mean, rstd, lnm.weight.data, self._g(lnm, "weight"), self._g(lnm, "bias"),
+                                         patch_hw=(h, w_))
+                else:
+                    dld = L.gemm_nt(dx, wt)
+                    dx = K.layernorm_bwd(dld, x, mean, rstd, lnm.weight.data, self._g(lnm, "weight"), self._g(lnm, "bias"),
+                                         patch_hw=(h, w_))
+                    del dld
             for bi in range(self.depths[si] - 1, -1, -1):
                 blk = f[1 + 2 * si][bi]
                 key = f"{si}.{bi}"
