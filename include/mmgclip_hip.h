@@ -418,6 +418,22 @@ int mmg_clip_labelled_rows_bwd_col(const float* X, const float* Y, const float* 
  * the same bits out on every rank and in every run.  N <= 16384, 1 <= k <= N. */
 int mmg_cluster_centroids(const float* T, const long long* labels, int N, int D, int k, float* out, mmg_stream_t stream);
 
+/* Sigmoid pairwise loss (SigLIP, Zhai et al. 2023; the reference has no such loss) of the n_loc local rows X against the N gathered
+ * rows Y (both L2-normalised, [.,D] fp32; D % 32 == 0, 32 <= D <= 1024), without an [n_loc,N] matrix in HBM:
+ *   z_ij = s <X_i,Y_j> + b   (s = *scale, the exponentiated scale; b = *bias; device scalars),   y_ij = +1 for a positive pair, else -1
+ *   positive: col_label == NULL ? j == diag_off + i : col_label[j] == row_key[i]   (int64 [N] / [n_loc]; both or neither)
+ * _fwd: row_loss[i] = sum_j softplus(-y_ij z_ij), softplus(u) = max(u,0) + log1p(exp(-|u|)).  One fp32 per row, written (not
+ *       accumulated) by its single owner in a fixed order, no atomics: bit-identical from run to run.
+ * _bwd: g_ij = coef * gout * (-y_ij) * sigmoid(-y_ij z_ij)   (gout: device scalar, NULL = 1);   dX[i,:] = s * sum_j g_ij Y[j,:] (written);
+ *       dscale += sum_ij g_ij <X_i,Y_j> (w.r.t. the exponentiated scale, as mmg_clip_rows_bwd_fused);  dbias += sum_ij g_ij;
+ *       either may be NULL; one float atomic per 32 rows each.
+ * Rows and columns the 32 x 32 tiles pad add exactly nothing.  Additive entry points: mmg_abi_version() stays 5. */
+int mmg_sigmoid_rows_fwd(const float* X, const float* Y, const float* scale, const float* bias, const long long* row_key,
+                         const long long* col_label, int n_loc, int N, int D, int diag_off, float* row_loss, mmg_stream_t stream);
+int mmg_sigmoid_rows_bwd(const float* X, const float* Y, const float* scale, const float* bias, const long long* row_key,
+                         const long long* col_label, const float* gout, float coef, int n_loc, int N, int D, int diag_off,
+                         float* dX, float* dscale, float* dbias, mmg_stream_t stream);
+
 /* ---- fp8 (OCP e4m3) forward GEMM path: BASELINE config C5 "ConvNeXt-base fp8 MFMA path" ---------------------------------
  * The reference has no reduced-precision path (its towers run torch fp32, mmgclip/networks/encoder.py:53,156); these replace
  * the same nn.Linear forwards of torchvision's CNBlock as mmg_gemm_nt_bf16 does, on v_mfma_f32_16x16x128_f8f6f4 (twice the

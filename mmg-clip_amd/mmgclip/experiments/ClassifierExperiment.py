@@ -68,8 +68,9 @@ class ClassifierExperiment:
 
         loss_cls = create_loss(self.config.loss.config.loss_name)
         use_global = comm is not None and _get(config, "distributed.global_loss", True)
-        # `loss.config.fused` / `loss.config.similarity_threshold` (AveragedMedicalCLIPLoss) are handed over when present
-        loss_kw = {k: _get(config, f"loss.config.{k}", None) for k in ("fused", "similarity_threshold")}
+        # `loss.config.fused` / `loss.config.similarity_threshold` (AveragedMedicalCLIPLoss) and `loss.config.positives`
+        # (SigmoidCLIPLoss) are handed over when present
+        loss_kw = {k: _get(config, f"loss.config.{k}", None) for k in ("fused", "similarity_threshold", "positives")}
         loss_kw = {k: v for k, v in loss_kw.items() if v is not None}
         self._criterion_takes_comm = True
         try:

@@ -326,6 +326,105 @@ def fused_averaged_loss(image_embeddings, text_embeddings, logit_scale, threshol
     return FusedAveragedLoss.apply(image_embeddings, text_embeddings, logit_scale, float(threshold), comm)
 
 
+class _HipSigmoidBackend:
+    """The product arithmetic of the fused sigmoid pairwise loss: the two entry points of csrc/sigmoid_head.hip and the row reduction
+    of the head.  As with `_HipHeadBackend`, no product signature selects anything else; tests/test_sigmoid_loss_cpu.py replaces this
+    module attribute in its worker processes (gloo, CPU).  `row_key` / `col_label` None = the diagonal at `diag_off`."""
+
+    @staticmethod
+    def rows_forward(x_loc, y_all, scale, bias, row_key, col_label, diag_off):
+        _hip.require_gpu(x_loc, y_all, scale, bias, row_key, col_label)
+        n_loc, D = x_loc.shape
+        row_loss = torch.empty(n_loc, device=x_loc.device, dtype=torch.float32)
+        call("mmg_sigmoid_rows_fwd", ptr(x_loc), ptr(y_all), ptr(scale), ptr(bias), ptr(row_key), ptr(col_label), n_loc,
+             y_all.shape[0], D, diag_off, ptr(row_loss), stream())
+        return row_loss
+
+    @staticmethod
+    def loss_sum(row_loss, coef):
+        """coef * sum(row_loss): the head's one-workgroup reduction with a zero `pos`."""
+        loss = torch.zeros(1, device=row_loss.device, dtype=torch.float32)
+        call("mmg_clip_loss_reduce", ptr(row_loss), ptr(torch.zeros_like(row_loss)), None, None, row_loss.shape[0], coef, ptr(loss),
+             stream())
+        return loss
+
+    @staticmethod
+    def rows_backward(x_loc, y_all, scale, bias, row_key, col_label, gout, coef, diag_off, dscale=None, dbias=None):
+        """dX (fresh); `dscale` / `dbias` ([1] tensors or None) are accumulated into."""
+        n_loc, D = x_loc.shape
+        dx = torch.empty_like(x_loc)
+        call("mmg_sigmoid_rows_bwd", ptr(x_loc), ptr(y_all), ptr(scale), ptr(bias), ptr(row_key), ptr(col_label), ptr(gout), coef,
+             n_loc, y_all.shape[0], D, diag_off, ptr(dx), ptr(dscale), ptr(dbias), stream())
+        return dx
+
+
+SIGMOID_POSITIVES = ("diagonal", "clusters")
+
+
+class FusedSigmoidLoss(torch.autograd.Function):
+    """Sigmoid pairwise loss (SigLIP, Zhai et al. 2023) over (already L2-normalised) embeddings of the GLOBAL batch, no [n,N] matrix.
+
+    loss = (1/N) sum_{i,j} softplus(-y_ij (s <I_i, T_j> + b)),  y_ij = +1 for a positive pair, -1 otherwise, N = global rows.
+    positives "diagonal": pair (i, i).  "clusters": every (i, j) whose texts fall into one greedy-threshold cluster, the clustering
+    of `FusedAveragedLoss` (same kernels, same threshold) on the gathered text - every rank clusters the same bits.
+    ONE exchange: the all-gather of the two embedding matrices (plus the all-reduce of the scalar loss); a pair's term needs no
+    normaliser from another rank.  Gradients are d(global loss)/d(local rows) and complete locally; d loss / d scale and d loss / d bias
+    are the LOCAL rows' share (counted once, by the image-side launch) and are summed over ranks by GradSync.  The labels carry no
+    gradient.  Returns (loss, labels of the local rows)."""
+
+    @staticmethod
+    def forward(ctx, img, txt, scale, bias, positives, threshold, comm):
+        be, cl = _HipSigmoidBackend, _HipAveragedBackend
+        if positives not in SIGMOID_POSITIVES:
+            raise ValueError(f"positives must be one of {SIGMOID_POSITIVES}, got {positives!r}")
+        img, txt = _f32c(img), _f32c(txt)
+        scale, bias = _f32c(scale.reshape(1)), _f32c(bias.reshape(1))
+        n_loc, D = img.shape
+        active = comm is not None and comm.active
+        if not active:
+            img_all, txt_all, off, N = img, txt, 0, n_loc
+        else:
+            img_all, txt_all = comm.all_gather_rows(img), comm.all_gather_rows(txt)
+            off, N = comm.rank * n_loc, n_loc * comm.world_size
+        if positives == "clusters":
+            labels, _, _ = cl.cluster(txt_all, threshold)
+            labels = labels.contiguous()
+            key = labels[off:off + n_loc].contiguous()
+            out_labels = key
+        else:
+            labels = key = None
+            out_labels = torch.arange(off, off + n_loc, device=img.device)
+        row_loss = be.rows_forward(img, txt_all, scale, bias, key, labels, off)
+        loss = be.loss_sum(row_loss, 1.0 / N)
+        if active:
+            loss = comm.all_reduce_sum(loss)
+        saved = [img, txt, scale, bias, img_all, txt_all] + ([key, labels] if labels is not None else [])
+        ctx.save_for_backward(*saved)
+        ctx.off, ctx.N, ctx.be = off, N, be
+        ctx.mark_non_differentiable(out_labels)
+        return loss.reshape(()), out_labels
+
+    @staticmethod
+    def backward(ctx, gout, _dlabels):
+        img, txt, scale, bias, img_all, txt_all = ctx.saved_tensors[:6]
+        key, labels = ctx.saved_tensors[6:] if len(ctx.saved_tensors) > 6 else (None, None)
+        be, off = ctx.be, ctx.off
+        gout = _f32c(gout.reshape(1))
+        coef = 1.0 / ctx.N
+        dscale = torch.zeros(1, device=img.device, dtype=torch.float32)
+        dbias = torch.zeros(1, device=img.device, dtype=torch.float32)
+        # y is symmetric (j == off + i  <=>  i == j - off; label equality), so the same keys serve both sides; every pair's share of
+        # the two scalars is counted once, by the image-side launch
+        dimg = be.rows_backward(img, txt_all, scale, bias, key, labels, gout, coef, off, dscale, dbias)
+        dtxt = be.rows_backward(txt, img_all, scale, bias, key, labels, gout, coef, off, None, None)
+        return dimg, dtxt, dscale.reshape(()), dbias.reshape(()), None, None, None
+
+
+def fused_sigmoid_loss(image_embeddings, text_embeddings, logit_scale, logit_bias, positives="diagonal", threshold=0.65, comm=None):
+    """Sigmoid pairwise loss on normalised embeddings -> (loss, labels_of_local_rows); `logit_scale` is the exponentiated scale."""
+    return FusedSigmoidLoss.apply(image_embeddings, text_embeddings, logit_scale, logit_bias, positives, float(threshold), comm)
+
+
 class ClusterMeanCols(torch.autograd.Function):
     """[n,N] logits -> [n,k] per-cluster column means (losses.py:164-186) and the matching gradient."""
 

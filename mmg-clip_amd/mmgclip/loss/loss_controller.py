@@ -1,4 +1,4 @@
-from .losses import CLIPLoss, AveragedMedicalCLIPLoss, MMGCLIPLoss  # noqa: F401
+from .losses import CLIPLoss, AveragedMedicalCLIPLoss, MMGCLIPLoss, SigmoidCLIPLoss  # noqa: F401
 
 
 def create_loss(loss_name):

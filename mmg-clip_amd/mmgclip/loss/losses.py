@@ -100,3 +100,30 @@ class AveragedMedicalCLIPLoss(nn.Module):
         loss_i = head.cross_entropy(averaged, labels)
         loss_t = head.cross_entropy(logits_per_text, labels)      # as the reference: [n,n] logits vs cluster ids
         return (loss_i + loss_t) / 2, labels
+
+
+class SigmoidCLIPLoss(nn.Module):
+    """Sigmoid pairwise loss (SigLIP, Zhai et al. 2023): (1/N) sum_ij softplus(-y_ij (s <I_i,T_j> + b)).  The reference has no such
+    loss; it is an additive choice next to the three softmax losses above.
+
+    Every (image, text) pair is scored on its own, so nothing is normalised across the batch, several positives per row are natural
+    and the global-batch form needs ONE exchange (the embedding all-gather).  `positives`:
+      "diagonal"  pair (i, i) alone is positive;
+      "clusters"  every pair whose texts fall into one cluster of `AveragedMedicalCLIPLoss`'s greedy threshold clustering
+                  (`similarity_threshold`) is positive: duplicates of a prompt are no longer each other's negatives.
+    There is one path, `head.fused_sigmoid_loss`, from the normalised embeddings; the [n,n] logits are never read.  The model
+    supplies `logit_bias` (a learnable 0-d parameter it creates for this loss)."""
+
+    needs_logits = False
+
+    def __init__(self, positives="diagonal", similarity_threshold=0.65, comm=None):
+        super().__init__()
+        if positives not in head.SIGMOID_POSITIVES:
+            raise ValueError(f"positives must be one of {head.SIGMOID_POSITIVES}, got {positives!r}")
+        self.positives = positives
+        self.similarity_threshold = similarity_threshold
+        self.comm = comm          # mmgclip.distributed.Comm for the global-batch loss (None = local batch)
+
+    def forward(self, image_embeddings, text_embeddings, logit_scale, logit_bias, **kwargs):
+        return head.fused_sigmoid_loss(image_embeddings, text_embeddings, logit_scale, logit_bias, self.positives,
+                                       self.similarity_threshold, self.comm)

@@ -89,6 +89,10 @@ class MMGCLIP(nn.Module):
             self.logit_scale = nn.Parameter(init.float().to(self.device))
         else:
             self.register_buffer("logit_scale", init.float().to(self.device), persistent=False)
+        # the sigmoid pairwise loss alone has a bias: with any other loss there is no parameter and no output key
+        if self.config.loss.config.loss_name == "SigmoidCLIPLoss":
+            bias = _get(self.config, "loss.config.logit_bias", -10.0)
+            self.logit_bias = nn.Parameter(torch.tensor(-10.0 if bias is None else float(bias), dtype=torch.float32).to(self.device))
 
     def count_parameters(self, model):
         """Logs a table of trainable parameters and returns their total count (mmgclip_model.py:54-74)."""
@@ -235,6 +239,8 @@ class MMGCLIP(nn.Module):
         logit_scale = self.logit_scale.exp()                               # :132
 
         output = {"image_embeddings": image_embeddings, "text_embeddings": text_embeddings, "logit_scale": logit_scale}
+        if self.config.loss.config.loss_name == "SigmoidCLIPLoss":
+            output["logit_bias"] = self.logit_bias
         if kwargs.get("materialize_logits", True):
             li, lt = head.ScaledLogits.apply(image_embeddings, text_embeddings, logit_scale)   # :135-136
             output["logits_per_image"], output["logits_per_text"] = li, lt

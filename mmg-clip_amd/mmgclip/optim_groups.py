@@ -12,7 +12,8 @@ Layer ids, read from the tower-relative names (the names the arenas use), k of L
   BERT      embeddings.* -> 0; encoder.layer.{i}.* -> i + 1; pooler.* -> L = number of layers
   ViT       conv_proj.*, class_token, encoder.pos_embedding -> 0; encoder_layer_{i} -> i + 1; encoder.ln.* -> L = number of layers
   ResNet    none (only layer4 trains)
-Projection heads and logit_scale are no tower's: neither layer_decay nor a tower multiplier touches them."""
+Projection heads, logit_scale and logit_bias (the sigmoid loss's) are no tower's: neither layer_decay nor a tower multiplier touches
+them; the two 0-d scalars are in the no-decay set at the base learning rate."""
 import math
 import re
 
@@ -73,7 +74,7 @@ def layer_ids(names):
 
 def is_no_decay(name, param):
     """The parameters every published ConvNeXt / ViT / BERT recipe keeps out of weight decay."""
-    return param.ndim <= 1 or name.endswith("layer_scale") or name.endswith("class_token") or name.endswith("encoder.pos_embedding")
+    return param.ndim <= 1 or name in ("logit_scale", "logit_bias") or name.endswith("layer_scale") or name.endswith("class_token") or name.endswith("encoder.pos_embedding")
 
 
 def _check(layer_decay, mults):
