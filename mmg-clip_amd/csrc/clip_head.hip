@@ -11,8 +11,9 @@
 // issued "swapped" (A = Y tile, B = X tile) so each lane holds ONE row i (its column of the
 // accumulator) and 16 columns j in registers: the row max / sum of the softmax are register-local
 // and need a single lane^32 shuffle at the end.  In the backward the accumulator registers are fed
-// back as the A operand of the second product (dX = G Y) with no lane movement.
-#include "clip_tile.h"      // CLIP_ROWS / CLIP_THREADS / NEG_BIG, acc_row, zt_tile, stage_x (shared with averaged_head.hip)
+// back as the A operand of the second product (dX = G Y) with no lane movement.  Both kernels are
+// written once in clip_tile.h for all three heads; this file holds CLIP's label source and pair rules.
+#include "clip_tile.h"
 
 // ---------------------------------------------------------------------------------------------
 // L2 normalise rows (no epsilon, as the reference): y = x / ||x||_2
@@ -47,214 +48,6 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
     const float inv = 1.0f / norm[r];
     float* dr = dx + (size_t)r * D;
     for (int c = lane; c < D; c += 64) dr[c] = (gr[c] - yr[c] * s) * inv;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Forward: per local row i, lse[i] = logsumexp_j(s <X_i, Y_j>) and pos[i] = s <X_i, Y_{label(i)}>.
-// label(i) = diag_off + i (the positive of local row i in the gathered matrix).  Optionally writes the logits.
-// ---------------------------------------------------------------------------------------------
-template <bool WRITE_LOGITS>
-__global__ __launch_bounds__(CLIP_THREADS) void clip_rows_fwd_kernel(
-    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ scale_ptr, int n_loc, int N,
-    int D, int diag_off, float* __restrict__ lse, float* __restrict__ pos, float* __restrict__ logits, int ldl) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int xld = D + 4;
-    float* Xs = smem;                       // [32][xld]
-    float* red = smem + CLIP_ROWS * xld;    // [4 waves][32 rows][3] (m, l, pos)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int il = lane & 31, h = lane >> 5;
-    const int i0 = blockIdx.x * CLIP_ROWS;
-    const int ig = i0 + il;
-    const float scale = *scale_ptr;
-
-    stage_x(X, Xs, i0, n_loc, D, xld);
-    __syncthreads();
-
-    float m = NEG_BIG, l = 0.f, p = 0.f;
-    const int lab = diag_off + ig;
-    const int ntiles = (N + 31) / 32;
-    for (int jt = wave; jt < ntiles; jt += 4) {
-        const int j0 = jt * 32;
-        const float* yrow = Y + (size_t)min(j0 + il, N - 1) * D;
-        const f32x16 acc = zt_tile(yrow, Xs + il * xld, D, h);
-        float z[16];
-        float tmax = NEG_BIG;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int j = j0 + acc_row(r, h);
-            z[r] = acc[r] * scale;
-            if (j < N) {
-                tmax = fmaxf(tmax, z[r]);
-                if (j == lab) p = z[r];
-            }
-        }
-        const float mn = fmaxf(m, tmax);
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int j = j0 + acc_row(r, h);
-            if (j < N) s += __expf(z[r] - mn);
-        }
-        l = l * __expf(m - mn) + s;
-        m = mn;
-        if (WRITE_LOGITS && ig < n_loc) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = j0 + 8 * q + 4 * h;
-                float* dst = logits + (size_t)ig * ldl + j;
-                if (j + 3 < N && ((ldl & 3) == 0)) {
-                    *reinterpret_cast<float4*>(dst) = make_float4(z[4 * q], z[4 * q + 1], z[4 * q + 2], z[4 * q + 3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (j + e < N) dst[e] = z[4 * q + e];
-                }
-            }
-        }
-    }
-    // combine the two lane halves (same row i, disjoint columns)
-    {
-        const float m2 = __shfl_xor(m, 32, 64), l2 = __shfl_xor(l, 32, 64), p2 = __shfl_xor(p, 32, 64);
-        const float mn = fmaxf(m, m2);
-        l = l * __expf(m - mn) + l2 * __expf(m2 - mn);
-        m = mn;
-        p += p2;
-    }
-    if (h == 0) {
-        red[(wave * 32 + il) * 3 + 0] = m;
-        red[(wave * 32 + il) * 3 + 1] = l;
-        red[(wave * 32 + il) * 3 + 2] = p;
-    }
-    __syncthreads();
-    if (threadIdx.x < 32 && i0 + threadIdx.x < n_loc) {
-        float mm = NEG_BIG, ll = 0.f, pp = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float m2 = red[(w * 32 + threadIdx.x) * 3 + 0], l2 = red[(w * 32 + threadIdx.x) * 3 + 1];
-            const float mn = fmaxf(mm, m2);
-            ll = ll * __expf(mm - mn) + l2 * __expf(m2 - mn);
-            mm = mn;
-            pp += red[(w * 32 + threadIdx.x) * 3 + 2];
-        }
-        lse[i0 + threadIdx.x] = mm + __logf(ll);
-        pos[i0 + threadIdx.x] = pp;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Backward of the rows: dX[i,:] = s * sum_j g_ij Y[j,:],  dscale += sum_ij g_ij <X_i,Y_j>
-//   FUSED : g_ij = coef * (exp(z_ij - lse_row[i]) + exp(z_ij - lse_col[j]) - 2 [j == diag_off+i])
-//           (the gradient of the symmetric CE w.r.t. z_ij when lse_row / lse_col are the row and the
-//            column log-sum-exps of the GLOBAL logit matrix; coef = dloss / (2 N_global))
-//   DENSE : g_ij = Ga[i*lda + j] + Gb[j*ldb + i]   (upstream gradients of materialised logits and of
-//            their transposed twin, either may be null)
-// NDT = 32-wide d tiles per wave (D <= 128*NDT).
-// ---------------------------------------------------------------------------------------------
-template <bool FUSED, int NDT>
-__global__ __launch_bounds__(CLIP_THREADS) void clip_rows_bwd_kernel(
-    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ scale_ptr,
-    const float* __restrict__ lse_row, const float* __restrict__ lse_col, const float* __restrict__ gout, float coef,
-    const float* __restrict__ Ga, int lda, const float* __restrict__ Gb, int ldb, int n_loc, int N, int D,
-    int diag_off, float* __restrict__ dX, float* __restrict__ dscale) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int xld = D + 4;
-    float* Xs = smem;                      // [32][xld]
-    float* Gs = smem + CLIP_ROWS * xld;    // [4 slots][32 j][33]
-    float* red = Gs + 4 * 32 * 33;         // [4]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int il = lane & 31, h = lane >> 5;
-    const int i0 = blockIdx.x * CLIP_ROWS;
-    const int ig = i0 + il;
-    const float scale = *scale_ptr;
-    const float c_up = FUSED ? coef * (gout ? *gout : 1.0f) : 1.0f;
-
-    stage_x(X, Xs, i0, n_loc, D, xld);
-    __syncthreads();
-
-    f32x16 dacc[NDT];
-#pragma unroll
-    for (int t = 0; t < NDT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dacc[t][r] = 0.f;
-
-    const float lr = (FUSED && ig < n_loc) ? lse_row[ig] : 0.f;
-    const int lab = diag_off + ig;
-    float ds = 0.f;
-    const int ntiles = (N + 31) / 32;
-    const int ndtiles = D / 32;
-    for (int jt0 = 0; jt0 < ntiles; jt0 += 4) {
-        const int jt = jt0 + wave;
-        float* Gw = Gs + wave * 32 * 33;
-        if (jt < ntiles) {
-            const int j0 = jt * 32;
-            const float* yrow = Y + (size_t)min(j0 + il, N - 1) * D;
-            const f32x16 acc = zt_tile(yrow, Xs + il * xld, D, h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int jl = acc_row(r, h);
-                const int j = j0 + jl;
-                float g = 0.f;
-                if (j < N && ig < n_loc) {
-                    if (FUSED) {
-                        const float z = acc[r] * scale;
-                        g = __expf(z - lr) + __expf(z - lse_col[j]);
-                        if (j == lab) g -= 2.0f;
-                        g *= c_up;
-                    } else {
-                        if (Ga) g += Ga[(size_t)ig * lda + j];
-                        if (Gb) g += Gb[(size_t)j * ldb + ig];
-                    }
-                    ds += g * acc[r];
-                }
-                Gw[jl * 33 + il] = g;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Gw[acc_row(r, h) * 33 + il] = 0.f;
-        }
-        __syncthreads();
-        // second product: every wave takes its d tiles over the 4 freshly written G tiles
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int j0 = (jt0 + s) * 32;
-            if (j0 < N) {
-                const float* Gsl = Gs + s * 32 * 33;
-#pragma unroll
-                for (int t = 0; t < NDT; ++t) {
-                    const int dt = wave + 4 * t;
-                    if (dt < ndtiles) {
-                        const float* ycol = Y + dt * 32 + il;
-#pragma unroll
-                        for (int kk = 0; kk < 16; ++kk) {
-                            const int jl = 2 * kk + h;
-                            const float a = Gsl[jl * 33 + il];                             // A[i][k=jl]
-                            const float b = ycol[(size_t)min(j0 + jl, N - 1) * D];          // B[k=jl][d]
-                            dacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, dacc[t], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // dX tile: lane holds column d = dt*32 + il, rows acc_row(r,h)
-#pragma unroll
-    for (int t = 0; t < NDT; ++t) {
-        const int dt = wave + 4 * t;
-        if (dt < ndtiles) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + acc_row(r, h);
-                if (i < n_loc) dX[(size_t)i * D + dt * 32 + il] = dacc[t][r] * scale;
-            }
-        }
-    }
-    if (dscale) {
-        ds = wave_sum(ds);
-        if (lane == 0) red[wave] = ds;
-        __syncthreads();
-        if (threadIdx.x == 0) atomicAdd(dscale, red[0] + red[1] + red[2] + red[3]);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -336,62 +129,78 @@ MMG_API int mmg_l2norm_bwd(const float* y, const float* norm, const float* dy, f
     return 0;
 }
 
-static int clip_check_dims(const char* who, int n_loc, int N, int D) {
-    MMG_CHECK_ARG(n_loc > 0 && N > 0, "%s: n_loc=%d N=%d must be positive", who, n_loc, N);
-    MMG_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= 1024, "%s: D=%d must be a multiple of 32 in [32,1024]", who, D);
-    return 0;
-}
+// label(i) = diag_off + i: the positive of local row i in the gathered matrix
+struct DiagLabel {
+    using arg = int;
+    using type = int;
+    static constexpr const char* NOTE = "rows_lse_fwd_kernel<DiagLabel, %s>";
+    static __device__ __forceinline__ int of(int diag_off, int ig, int) { return diag_off + ig; }
+};
 
 MMG_API int mmg_clip_rows_fwd(const float* X, const float* Y, const float* scale, int n_loc, int N, int D,
                               int diag_off, float* lse, float* pos, float* logits, int ldl, hipStream_t stream) {
-    if (clip_check_dims("mmg_clip_rows_fwd", n_loc, N, D)) return 1;
+    if (rows_check_dims("mmg_clip_rows_fwd", n_loc, N, D)) return 1;
     MMG_CHECK_ARG(X && Y && scale && lse && pos, "mmg_clip_rows_fwd: null pointer");
     MMG_CHECK_ARG(!logits || ldl >= N, "mmg_clip_rows_fwd: ldl=%d < N=%d", ldl, N);
-    const size_t shm = (size_t)(CLIP_ROWS * (D + 4) + 4 * 32 * 3) * sizeof(float);
-    const dim3 grid(cdiv(n_loc, CLIP_ROWS));
-    if (logits) {
-        mmg_allow_lds(clip_rows_fwd_kernel<true>, shm);
-        hipLaunchKernelGGL(clip_rows_fwd_kernel<true>, grid, dim3(CLIP_THREADS), shm, stream, X, Y, scale, n_loc, N, D,
-                           diag_off, lse, pos, logits, ldl);
-    } else {
-        mmg_allow_lds(clip_rows_fwd_kernel<false>, shm);
-        hipLaunchKernelGGL(clip_rows_fwd_kernel<false>, grid, dim3(CLIP_THREADS), shm, stream, X, Y, scale, n_loc, N, D,
-                           diag_off, lse, pos, (float*)nullptr, 0);
-    }
+    if (logits) launch_rows_lse_fwd<DiagLabel, true>(X, Y, scale, diag_off, n_loc, N, D, lse, pos, logits, ldl, stream);
+    else launch_rows_lse_fwd<DiagLabel, false>(X, Y, scale, diag_off, n_loc, N, D, lse, pos, nullptr, 0, stream);
     MMG_LAUNCH_CHECK("mmg_clip_rows_fwd");
     return 0;
 }
 
-template <bool FUSED>
-static int launch_rows_bwd(const float* X, const float* Y, const float* scale, const float* lse_row,
-                           const float* lse_col, const float* gout, float coef, const float* Ga, int lda,
-                           const float* Gb, int ldb, int n_loc, int N, int D, int diag_off, float* dX, float* dscale,
-                           hipStream_t stream) {
-    const size_t shm = (size_t)(CLIP_ROWS * (D + 4) + 4 * 32 * 33 + 4) * sizeof(float);
-    const dim3 grid(cdiv(n_loc, CLIP_ROWS));
-    const int ndt = (D + 127) / 128;
-#define LAUNCH_BWD(NDT)                                                                                               \
-    do {                                                                                                              \
-        mmg_allow_lds(clip_rows_bwd_kernel<FUSED, NDT>, shm);                                                         \
-        hipLaunchKernelGGL((clip_rows_bwd_kernel<FUSED, NDT>), grid, dim3(CLIP_THREADS), shm, stream, X, Y, scale,    \
-                           lse_row, lse_col, gout, coef, Ga, lda, Gb, ldb, n_loc, N, D, diag_off, dX, dscale);        \
-    } while (0)
-    if (ndt <= 1) LAUNCH_BWD(1);
-    else if (ndt == 2) LAUNCH_BWD(2);
-    else if (ndt <= 4) LAUNCH_BWD(4);
-    else LAUNCH_BWD(8);
-#undef LAUNCH_BWD
-    return 0;
-}
+// Pair rules of rows_bwd_kernel (clip_tile.h), with z_ij = s <X_i, Y_j>:
+//   fused : g_ij = coef * gout * (exp(z_ij - lse_row[i]) + exp(z_ij - lse_col[j]) - 2 [j == diag_off+i])
+//           (the gradient of the symmetric CE w.r.t. z_ij when lse_row / lse_col are the row and the
+//            column log-sum-exps of the GLOBAL logit matrix; coef = dloss / (2 N_global))
+//   dense : g_ij = Ga[i*lda + j] + Gb[j*ldb + i]   (upstream gradients of materialised logits and of
+//            their transposed twin, either may be null)
+struct ClipFusedPair {
+    static constexpr bool DSCALE = true, DBIAS = false, ACCUMULATE = false;
+    static constexpr const char* NOTE = "rows_bwd_kernel<ClipFusedPair, %d>";
+    const float *lse_row, *lse_col, *gout;
+    float coef;
+    int diag_off;
+    struct Row {
+        float lr, c_up;
+        int lab;
+    };
+    __device__ __forceinline__ Row row(int ig, int n_loc) const {
+        return {ig < n_loc ? lse_row[ig] : 0.f, coef * (gout ? *gout : 1.0f), diag_off + ig};
+    }
+    __device__ __forceinline__ float g(const Row& w, float dot, float scale, int j) const {
+        const float z = dot * scale;
+        float g = __expf(z - w.lr) + __expf(z - lse_col[j]);
+        if (j == w.lab) g -= 2.0f;
+        return g * w.c_up;
+    }
+};
 
-// Fused symmetric-CE gradient of the rows (see kernel comment).  dscale (may be null) is ACCUMULATED.
+struct ClipDensePair {
+    static constexpr bool DSCALE = true, DBIAS = false, ACCUMULATE = false;
+    static constexpr const char* NOTE = "rows_bwd_kernel<ClipDensePair, %d>";
+    const float* Ga;
+    int lda;
+    const float* Gb;
+    int ldb;
+    struct Row {
+        int ig;
+    };
+    __device__ __forceinline__ Row row(int ig, int) const { return {ig}; }
+    __device__ __forceinline__ float g(const Row& w, float, float, int j) const {
+        float g = 0.f;
+        if (Ga) g += Ga[(size_t)w.ig * lda + j];
+        if (Gb) g += Gb[(size_t)j * ldb + w.ig];
+        return g;
+    }
+};
+
+// Fused symmetric-CE gradient of the rows.  dscale (may be null) is ACCUMULATED.
 MMG_API int mmg_clip_rows_bwd_fused(const float* X, const float* Y, const float* scale, const float* lse_row,
                                     const float* lse_col, const float* gout, float coef, int n_loc, int N, int D,
                                     int diag_off, float* dX, float* dscale, hipStream_t stream) {
-    if (clip_check_dims("mmg_clip_rows_bwd_fused", n_loc, N, D)) return 1;
+    if (rows_check_dims("mmg_clip_rows_bwd_fused", n_loc, N, D)) return 1;
     MMG_CHECK_ARG(X && Y && scale && lse_row && lse_col && dX, "mmg_clip_rows_bwd_fused: null pointer");
-    launch_rows_bwd<true>(X, Y, scale, lse_row, lse_col, gout, coef, nullptr, 0, nullptr, 0, n_loc, N, D, diag_off, dX,
-                          dscale, stream);
+    launch_rows_bwd(X, Y, scale, ClipFusedPair{lse_row, lse_col, gout, coef, diag_off}, n_loc, N, D, 0, dX, dscale, nullptr, stream);
     MMG_LAUNCH_CHECK("mmg_clip_rows_bwd_fused");
     return 0;
 }
@@ -400,11 +209,10 @@ MMG_API int mmg_clip_rows_bwd_fused(const float* X, const float* Y, const float*
 MMG_API int mmg_clip_rows_bwd_dense(const float* X, const float* Y, const float* scale, const float* Ga, int lda,
                                     const float* Gb, int ldb, int n_loc, int N, int D, float* dX, float* dscale,
                                     hipStream_t stream) {
-    if (clip_check_dims("mmg_clip_rows_bwd_dense", n_loc, N, D)) return 1;
+    if (rows_check_dims("mmg_clip_rows_bwd_dense", n_loc, N, D)) return 1;
     MMG_CHECK_ARG(X && Y && scale && dX && (Ga || Gb), "mmg_clip_rows_bwd_dense: null pointer");
     MMG_CHECK_ARG((!Ga || lda >= N) && (!Gb || ldb >= n_loc), "mmg_clip_rows_bwd_dense: bad leading dimension");
-    launch_rows_bwd<false>(X, Y, scale, nullptr, nullptr, nullptr, 1.0f, Ga, lda, Gb, ldb, n_loc, N, D, 0, dX, dscale,
-                           stream);
+    launch_rows_bwd(X, Y, scale, ClipDensePair{Ga, lda, Gb, ldb}, n_loc, N, D, 0, dX, dscale, nullptr, stream);
     MMG_LAUNCH_CHECK("mmg_clip_rows_bwd_dense");
     return 0;
 }

@@ -6,10 +6,11 @@
 //   positive: col_label == NULL ? j == diag_off + i : col_label[j] == row_key[i]
 //
 // Every pair stands alone: there is no row normaliser to carry from the forward to the backward, so the backward recomputes z and
-// needs nothing but the operands.  Tiling as averaged_head.hip: 32 local rows in LDS, 32-column tiles of Y streamed, four waves
-// (one workgroup pass covers 4 x 32 = 128 columns), fp32 v_mfma_f32_32x32x2_f32, the G tile fed back as the A operand of the
-// second product.  The tile helpers clamp rows >= n_loc and columns >= N to duplicates of the last valid one; a sigmoid has no
-// "minus infinity" that makes such a pair vanish for both signs of y, so a padded pair is SELECTED to zero below.
+// needs nothing but the operands.  Tiling as clip_tile.h has it: 32 local rows in LDS, 32-column tiles of Y streamed, four waves
+// (one workgroup pass covers 4 x 32 = 128 columns), fp32 v_mfma_f32_32x32x2_f32; the backward is rows_bwd_kernel under the rule
+// SigmoidPair.  The tile helpers clamp rows >= n_loc and columns >= N to duplicates of the last valid one; a sigmoid has no
+// "minus infinity" that makes such a pair vanish for both signs of y, so a padded pair is SELECTED to zero: below in the forward,
+// by the skeleton (not the rule) in the backward.
 #include "clip_tile.h"
 
 #define SIG_COLS_PER_PASS (4 * 32)
@@ -70,124 +71,12 @@ __global__ __launch_bounds__(CLIP_THREADS) void sigmoid_rows_fwd_kernel(
         row_loss[i0 + threadIdx.x] = (red[threadIdx.x] + red[32 + threadIdx.x]) + (red[64 + threadIdx.x] + red[96 + threadIdx.x]);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Backward: dX[i,:] = s * sum_j g_ij Y[j,:];  dscale += sum g_ij <X_i,Y_j>;  dbias += sum g_ij  (one atomic per workgroup each)
-// NDT = 32-wide d tiles per wave (D <= 128*NDT).
-// ---------------------------------------------------------------------------------------------
-template <int NDT>
-__global__ __launch_bounds__(CLIP_THREADS) void sigmoid_rows_bwd_kernel(
-    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ scale_ptr, const float* __restrict__ bias_ptr,
-    const long long* __restrict__ row_key, const long long* __restrict__ col_label, const float* __restrict__ gout, float coef,
-    int n_loc, int N, int D, int diag_off, float* __restrict__ dX, float* __restrict__ dscale, float* __restrict__ dbias) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int xld = D + 4;
-    float* Xs = smem;                      // [32][xld]
-    float* Gs = smem + CLIP_ROWS * xld;    // [4 slots][32 j][33]
-    float* red = Gs + 4 * 32 * 33;         // [2][4]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int il = lane & 31, h = lane >> 5;
-    const int i0 = blockIdx.x * CLIP_ROWS;
-    const int ig = i0 + il;
-    const float scale = *scale_ptr, bias = *bias_ptr;
-    const float c_up = coef * (gout ? *gout : 1.0f);
-
-    stage_x(X, Xs, i0, n_loc, D, xld);
-    __syncthreads();
-
-    f32x16 dacc[NDT];
-#pragma unroll
-    for (int t = 0; t < NDT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dacc[t][r] = 0.f;
-
-    const long long rk = col_label ? row_key[min(ig, n_loc - 1)] : (long long)diag_off + ig;
-    float ds = 0.f, db = 0.f;
-    const int ntiles = (N + 31) / 32;
-    const int ndtiles = D / 32;
-    for (int jt0 = 0; jt0 < ntiles; jt0 += 4) {
-        const int jt = jt0 + wave;
-        float* Gw = Gs + wave * 32 * 33;
-        if (jt < ntiles) {
-            const int j0 = jt * 32;
-            const float* yrow = Y + (size_t)min(j0 + il, N - 1) * D;
-            const f32x16 acc = zt_tile(yrow, Xs + il * xld, D, h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int jl = acc_row(r, h);
-                const int j = j0 + jl;
-                float g = 0.f;
-                if (j < N && ig < n_loc) {
-                    const float z = fmaf(acc[r], scale, bias);
-                    const bool positive = (col_label ? col_label[j] : (long long)j) == rk;
-                    g = positive ? -c_up * sig_sigmoid(-z) : c_up * sig_sigmoid(z);
-                    ds += g * acc[r];
-                    db += g;
-                }
-                Gw[jl * 33 + il] = g;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Gw[acc_row(r, h) * 33 + il] = 0.f;
-        }
-        __syncthreads();
-        // second product: every wave takes its d tiles over the 4 freshly written G tiles
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int j0 = (jt0 + s) * 32;
-            if (j0 < N) {
-                const float* Gsl = Gs + s * 32 * 33;
-#pragma unroll
-                for (int t = 0; t < NDT; ++t) {
-                    const int dt = wave + 4 * t;
-                    if (dt < ndtiles) {
-                        const float* ycol = Y + dt * 32 + il;
-#pragma unroll
-                        for (int kk = 0; kk < 16; ++kk) {
-                            const int jl = 2 * kk + h;
-                            const float a = Gsl[jl * 33 + il];                             // A[i][k=jl]
-                            const float b = ycol[(size_t)min(j0 + jl, N - 1) * D];          // B[k=jl][d]  (G is 0 on a clamped row)
-                            dacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, dacc[t], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // dX tile: lane holds column d = dt*32 + il, rows acc_row(r,h); every element has one owner
-#pragma unroll
-    for (int t = 0; t < NDT; ++t) {
-        const int dt = wave + 4 * t;
-        if (dt < ndtiles) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + acc_row(r, h);
-                if (i < n_loc) dX[(size_t)i * D + dt * 32 + il] = dacc[t][r] * scale;
-            }
-        }
-    }
-    if (dscale || dbias) {
-        ds = wave_sum(ds);
-        db = wave_sum(db);
-        if (lane == 0) {
-            red[wave] = ds;
-            red[4 + wave] = db;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (dscale) atomicAdd(dscale, (red[0] + red[1]) + (red[2] + red[3]));
-            if (dbias) atomicAdd(dbias, (red[4] + red[5]) + (red[6] + red[7]));
-        }
-    }
-}
-
 // =============================================================================================
 // C ABI
 // =============================================================================================
 static int sigmoid_check(const char* who, const void* X, const void* Y, const void* scale, const void* bias, const void* row_key,
                          const void* col_label, int n_loc, int N, int D, const void* out) {
-    MMG_CHECK_ARG(n_loc > 0 && N > 0, "%s: n_loc=%d N=%d must be positive", who, n_loc, N);
-    MMG_CHECK_ARG(D >= 32 && D % 32 == 0 && D <= 1024, "%s: D=%d must be a multiple of 32 in [32,1024]", who, D);
+    if (rows_check_dims(who, n_loc, N, D)) return 1;
     MMG_CHECK_ARG(X && Y && scale && bias && out, "%s: null pointer", who);
     MMG_CHECK_ARG((row_key != nullptr) == (col_label != nullptr), "%s: row_key and col_label come together (or both NULL: the diagonal)", who);
     return 0;
@@ -197,7 +86,7 @@ MMG_API int mmg_sigmoid_rows_fwd(const float* X, const float* Y, const float* sc
                                  const long long* col_label, int n_loc, int N, int D, int diag_off, float* row_loss,
                                  hipStream_t stream) {
     if (sigmoid_check("mmg_sigmoid_rows_fwd", X, Y, scale, bias, row_key, col_label, n_loc, N, D, row_loss)) return 1;
-    const size_t shm = (size_t)(CLIP_ROWS * (D + 4) + 4 * 32) * sizeof(float);
+    const size_t shm = rows_lds_bytes(D, 4 * 32);
     mmg_allow_lds(sigmoid_rows_fwd_kernel, shm);
     MMG_NOTE_KERNEL("sigmoid_rows_fwd_kernel");
     hipLaunchKernelGGL(sigmoid_rows_fwd_kernel, dim3(cdiv(n_loc, CLIP_ROWS)), dim3(CLIP_THREADS), shm, stream, X, Y, scale, bias,
@@ -206,25 +95,35 @@ MMG_API int mmg_sigmoid_rows_fwd(const float* X, const float* Y, const float* sc
     return 0;
 }
 
+// Pair rule of rows_bwd_kernel (clip_tile.h): g_ij = coef * gout * (-y_ij) * sigmoid(-y_ij z_ij); both scalars, dbias += sum g_ij
+struct SigmoidPair {
+    static constexpr bool DSCALE = true, DBIAS = true, ACCUMULATE = false;
+    static constexpr const char* NOTE = "sigmoid_rows_bwd_kernel<%d>";
+    const float* bias;
+    const long long *row_key, *col_label;
+    const float* gout;
+    float coef;
+    int diag_off;
+    struct Row {
+        long long key;
+        float bias, c_up;
+    };
+    __device__ __forceinline__ Row row(int ig, int n_loc) const {
+        return {col_label ? row_key[min(ig, n_loc - 1)] : (long long)diag_off + ig, *bias, coef * (gout ? *gout : 1.0f)};
+    }
+    __device__ __forceinline__ float g(const Row& w, float dot, float scale, int j) const {
+        const float z = fmaf(dot, scale, w.bias);
+        const bool positive = (col_label ? col_label[j] : (long long)j) == w.key;
+        return positive ? -w.c_up * sig_sigmoid(-z) : w.c_up * sig_sigmoid(z);
+    }
+};
+
+// dX[i,:] = s * sum_j g_ij Y[j,:];  dscale / dbias (may be null) are ACCUMULATED
 MMG_API int mmg_sigmoid_rows_bwd(const float* X, const float* Y, const float* scale, const float* bias, const long long* row_key,
                                  const long long* col_label, const float* gout, float coef, int n_loc, int N, int D, int diag_off,
                                  float* dX, float* dscale, float* dbias, hipStream_t stream) {
     if (sigmoid_check("mmg_sigmoid_rows_bwd", X, Y, scale, bias, row_key, col_label, n_loc, N, D, dX)) return 1;
-    const size_t shm = (size_t)(CLIP_ROWS * (D + 4) + 4 * 32 * 33 + 8) * sizeof(float);
-    const dim3 grid(cdiv(n_loc, CLIP_ROWS));
-    const int ndt = (D + 127) / 128;
-#define LAUNCH_SBWD(NDT)                                                                                                    \
-    do {                                                                                                                    \
-        mmg_allow_lds(sigmoid_rows_bwd_kernel<NDT>, shm);                                                                   \
-        MMG_NOTE_KERNEL("sigmoid_rows_bwd_kernel<%d>", NDT);                                                                \
-        hipLaunchKernelGGL((sigmoid_rows_bwd_kernel<NDT>), grid, dim3(CLIP_THREADS), shm, stream, X, Y, scale, bias,        \
-                           row_key, col_label, gout, coef, n_loc, N, D, diag_off, dX, dscale, dbias);                       \
-    } while (0)
-    if (ndt <= 1) LAUNCH_SBWD(1);
-    else if (ndt == 2) LAUNCH_SBWD(2);
-    else if (ndt <= 4) LAUNCH_SBWD(4);
-    else LAUNCH_SBWD(8);
-#undef LAUNCH_SBWD
+    launch_rows_bwd(X, Y, scale, SigmoidPair{bias, row_key, col_label, gout, coef, diag_off}, n_loc, N, D, 0, dX, dscale, dbias, stream);
     MMG_LAUNCH_CHECK("mmg_sigmoid_rows_bwd");
     return 0;
 }

@@ -1,4 +1,6 @@
-"""Host side of the contrastive head: autograd wrappers over the fp32 gfx950 kernels of csrc/clip_head.hip.
+"""Host side of the contrastive heads: autograd wrappers over the fp32 gfx950 kernels of csrc/clip_head.hip (CLIP),
+csrc/averaged_head.hip (AveragedMedicalCLIP) and csrc/sigmoid_head.hip (sigmoid pairwise), which share the tile skeleton of
+csrc/clip_tile.h.
 
 Reference arithmetic (path:line in the reference tree):
     mmgclip/networks/mmgclip_model.py:128-136  normalise, exp(logit_scale), two logit matmuls
@@ -15,6 +17,27 @@ def _f32c(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _gather_rows(comm, t):
+    """`t` of every rank, rank-major (`t` itself without an active communicator)."""
+    return comm.all_gather_rows(t) if comm is not None and comm.active else t
+
+
+def _global_batch(comm, img, txt, *scalars):
+    """What every fused loss starts from: (img, txt, img_all, txt_all, off, N, *scalars) - the local embeddings in fp32, both
+    matrices gathered over the ranks (exchange 1), the offset of the local rows in them, the global row count and each scalar
+    parameter as a [1] fp32 tensor."""
+    img, txt = _f32c(img), _f32c(txt)
+    n_loc = img.shape[0]
+    active = comm is not None and comm.active
+    off, N = (comm.rank * n_loc, n_loc * comm.world_size) if active else (0, n_loc)
+    return (img, txt, _gather_rows(comm, img), _gather_rows(comm, txt), off, N, *(_f32c(s.reshape(1)) for s in scalars))
+
+
+def _global_loss(comm, loss):
+    """The ranks' partial losses summed: the GLOBAL loss, identical on every rank."""
+    return comm.all_reduce_sum(loss) if comm is not None and comm.active else loss
 
 
 class L2Normalize(torch.autograd.Function):
@@ -164,22 +187,12 @@ class FusedClipLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, txt, scale, comm):
         be = _HipHeadBackend
-        img, txt = _f32c(img), _f32c(txt)
-        scale = _f32c(scale.reshape(1))
-        n_loc, D = img.shape
-        if comm is None or not comm.active:
-            img_all, txt_all, off, N = img, txt, 0, n_loc
-        else:
-            img_all, txt_all = comm.all_gather_rows(img), comm.all_gather_rows(txt)
-            off, N = comm.rank * n_loc, n_loc * comm.world_size
+        img, txt, img_all, txt_all, off, N, scale = _global_batch(comm, img, txt, scale)
         lse_i, pos_i = be.rows_forward(img, txt_all, scale, off)
         lse_t, pos_t = be.rows_forward(txt, img_all, scale, off)
         loss = be.loss_sum(lse_i, pos_i, lse_t, pos_t, 1.0 / (2.0 * N))
-        if comm is not None and comm.active:
-            lse_i_all, lse_t_all = comm.all_gather_rows(lse_i), comm.all_gather_rows(lse_t)
-            loss = comm.all_reduce_sum(loss)
-        else:
-            lse_i_all, lse_t_all = lse_i, lse_t
+        lse_i_all, lse_t_all = _gather_rows(comm, lse_i), _gather_rows(comm, lse_t)
+        loss = _global_loss(comm, loss)
         ctx.save_for_backward(img, txt, scale, img_all, txt_all, lse_i, lse_t, lse_i_all, lse_t_all)
         ctx.off, ctx.N, ctx.be = off, N, be
         return loss.reshape(())
@@ -282,26 +295,15 @@ class FusedAveragedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, txt, scale, threshold, comm):
         be = _HipAveragedBackend
-        img, txt = _f32c(img), _f32c(txt)
-        scale = _f32c(scale.reshape(1))
-        n_loc, D = img.shape
-        active = comm is not None and comm.active
-        if not active:
-            img_all, txt_all, off, N = img, txt, 0, n_loc
-        else:
-            img_all, txt_all = comm.all_gather_rows(img), comm.all_gather_rows(txt)
-            off, N = comm.rank * n_loc, n_loc * comm.world_size
+        img, txt, img_all, txt_all, off, N, scale = _global_batch(comm, img, txt, scale)
         labels, counts, k = be.cluster(txt_all, threshold)
         cent = be.centroids(txt_all, labels, k)
-        c_loc = labels[off:off + n_loc].contiguous()
+        c_loc = labels[off:off + img.shape[0]].contiguous()
         lse_i, pos_i = be.rows_forward(img, cent, scale, c_loc)
         lse_t, pos_t = be.rows_forward(txt, img_all, scale, c_loc)
         loss = be.loss_sum(lse_i, pos_i, lse_t, pos_t, 1.0 / (2.0 * N))
-        if active:
-            lse_i_all, lse_t_all = comm.all_gather_rows(lse_i), comm.all_gather_rows(lse_t)
-            loss = comm.all_reduce_sum(loss)
-        else:
-            lse_i_all, lse_t_all = lse_i, lse_t
+        lse_i_all, lse_t_all = _gather_rows(comm, lse_i), _gather_rows(comm, lse_t)
+        loss = _global_loss(comm, loss)
         ctx.save_for_backward(img, txt, scale, img_all, txt_all, cent, labels, counts, c_loc, lse_i, lse_t, lse_i_all, lse_t_all)
         ctx.off, ctx.N, ctx.be = off, N, be
         ctx.mark_non_differentiable(c_loc)
@@ -377,15 +379,8 @@ class FusedSigmoidLoss(torch.autograd.Function):
         be, cl = _HipSigmoidBackend, _HipAveragedBackend
         if positives not in SIGMOID_POSITIVES:
             raise ValueError(f"positives must be one of {SIGMOID_POSITIVES}, got {positives!r}")
-        img, txt = _f32c(img), _f32c(txt)
-        scale, bias = _f32c(scale.reshape(1)), _f32c(bias.reshape(1))
-        n_loc, D = img.shape
-        active = comm is not None and comm.active
-        if not active:
-            img_all, txt_all, off, N = img, txt, 0, n_loc
-        else:
-            img_all, txt_all = comm.all_gather_rows(img), comm.all_gather_rows(txt)
-            off, N = comm.rank * n_loc, n_loc * comm.world_size
+        img, txt, img_all, txt_all, off, N, scale, bias = _global_batch(comm, img, txt, scale, bias)
+        n_loc = img.shape[0]
         if positives == "clusters":
             labels, _, _ = cl.cluster(txt_all, threshold)
             labels = labels.contiguous()
@@ -395,9 +390,7 @@ class FusedSigmoidLoss(torch.autograd.Function):
             labels = key = None
             out_labels = torch.arange(off, off + n_loc, device=img.device)
         row_loss = be.rows_forward(img, txt_all, scale, bias, key, labels, off)
-        loss = be.loss_sum(row_loss, 1.0 / N)
-        if active:
-            loss = comm.all_reduce_sum(loss)
+        loss = _global_loss(comm, be.loss_sum(row_loss, 1.0 / N))
         saved = [img, txt, scale, bias, img_all, txt_all] + ([key, labels] if labels is not None else [])
         ctx.save_for_backward(*saved)
         ctx.off, ctx.N, ctx.be = off, N, be

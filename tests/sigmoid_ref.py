@@ -57,9 +57,10 @@ SB_PAIRS = ((10.0, -10.0), (14.2857, 0.0), (100.0, -12.0))
 
 # (n_loc, N, D, diag_off): the smallest shapes at which the tiling can go wrong - one pair; one partial tile; one tile and one row /
 # column more; three row tiles and the widest D (the NDT = 8 backward); one column more than a workgroup pass; a rank that is not
-# the first.  D = 32 / 64 / 512 / 1024 take the NDT = 1 / 1 / 4 / 8 instantiations of the backward; (34, 35, 256) is there for NDT = 2.
+# the first.  D = 32 / 64 / 512 / 1024 take the NDT = 1 / 1 / 4 / 8 instantiations of the backward; (34, 35, 256) and (33, 33, 256)
+# are there for NDT = 2.
 SHAPES = ((1, 1, 32, 0), (31, 31, 32, 0), (33, 33, 64, 0), (65, 65, 1024, 0), (32, COLS_PER_PASS + 1, 512, 0), (32, 96, 64, 64),
-          (34, 35, 256, 0))
+          (34, 35, 256, 0), (33, 33, 256, 0))
 MODES = ("diagonal", "clusters")
 
 

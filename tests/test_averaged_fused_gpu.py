@@ -27,8 +27,9 @@ LS = float(np.log(1 / 0.07))
 # (N, D, clusters): (8,32) one partial tile; (37,64) a partial row tile and a partial column tile; (130,160) more than one
 # 128-column round and D/32 not a multiple of 4; (256,512) the product shape.  k = 1, k = 3 (centroid matrix far below one tile),
 # k about N/4, and (130,160,40): cluster ids >= 32, so the text-side target column crosses a tile boundary.
+# (37,1024): the widest D, the only one that takes the NDT = 8 backward (D = 32, 64 take NDT = 1, 160 NDT = 2, 512 NDT = 4).
 CASES = [(8, 32, 1), (8, 32, 3), (37, 64, 1), (37, 64, 3), (37, 64, 9), (72, 64, 7), (72, 64, 18), (130, 160, 3), (130, 160, 40),
-         (256, 512, 1), (256, 512, 3), (256, 512, 64)]
+         (256, 512, 1), (256, 512, 3), (256, 512, 64), (37, 1024, 9)]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -100,7 +101,7 @@ def test_fused_loss_and_gradients_match_the_float64_oracle(dev, N, D, groups):
         assert fused <= 1.0, (name, figs)
 
 
-@pytest.mark.parametrize("N,D", [(8, 32), (37, 64), (72, 64), (256, 512)])
+@pytest.mark.parametrize("N,D", [(8, 32), (37, 64), (72, 64), (256, 512), (37, 1024)])
 def test_every_text_its_own_cluster_is_clip_loss(dev, N, D):
     """k = N: the centroids are the texts, the labels arange, and the loss is CLIPLoss - loss and all three gradients agree with
     `head.fused_clip_loss` on the same inputs."""
