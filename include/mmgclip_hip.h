@@ -434,6 +434,21 @@ int mmg_sigmoid_rows_bwd(const float* X, const float* Y, const float* scale, con
                          const long long* col_label, const float* gout, float coef, int n_loc, int N, int D, int diag_off,
                          float* dX, float* dscale, float* dbias, mmg_stream_t stream);
 
+/* Retrieval ranks (validation; the reference has no such metric): where the best positive of each of the n_loc local queries X stands
+ * among the negatives of the N gallery rows Y ([.,D] fp32; D % 32 == 0, 32 <= D <= 1024), without an [n_loc,N] matrix in HBM and
+ * without a sort.  s_ij = <X_i,Y_j>: no scale or bias (a positive scale does not change a rank).
+ *   positive: col_label == NULL ? j == diag_off + i : col_label[j] == row_key[i]   (int64 [N] / [n_loc]; both or neither; on the
+ *             diagonal 0 <= diag_off and diag_off + n_loc <= N)
+ *   n_pos[i] = number of positives;  best[i] = max of s_ij over them, -inf when there is none;
+ *   n_gt[i] / n_eq[i] = number of NEGATIVE j with s_ij > best[i] / s_ij == best[i]   (a positive never counts; with no positive
+ *             every column is a negative above -inf).  The host takes rank_i = 1 + n_gt[i] + n_eq[i]: ties count against the model.
+ * One launch, two sweeps over Y (the threshold, then the counts), both through the same MFMA chain, so `==` compares equal bits.
+ * Integer counts, one owner per row, a fixed tree, no atomics: bit-identical from run to run and however the queries are split over
+ * launches.  Rows and columns the 32 x 32 tiles pad are never counted or written.  FINITE inputs are assumed: a NaN score compares
+ * false both ways and is not defined here.  Additive entry point: mmg_abi_version() stays 5. */
+int mmg_retrieval_rows_rank(const float* X, const float* Y, const long long* row_key, const long long* col_label, int n_loc, int N,
+                            int D, int diag_off, float* best, int* n_pos, int* n_gt, int* n_eq, mmg_stream_t stream);
+
 /* ---- fp8 (OCP e4m3) forward GEMM path: BASELINE config C5 "ConvNeXt-base fp8 MFMA path" ---------------------------------
  * The reference has no reduced-precision path (its towers run torch fp32, mmgclip/networks/encoder.py:53,156); these replace
  * the same nn.Linear forwards of torchvision's CNBlock as mmg_gemm_nt_bf16 does, on v_mfma_f32_16x16x128_f8f6f4 (twice the

@@ -10,7 +10,8 @@ Additive options: `distributed.global_loss`, `optimizer.config.fused` (FusedAdam
 `optimizer.config.max_grad_norm` / `optimizer.config.skip_nonfinite` (clip the gradients by their global norm and do not step on a
 NaN / Inf gradient; the reference goes from backward straight to step, :115-118, and so does a shipped config),
 `optimizer.config.layer_decay` / `no_decay_1d` / `image_lr_mult` / `text_lr_mult` (param groups, optim_groups.py; absent from the
-shipped configs, and then AdamW gets `model.parameters()` as its one group, :74).
+shipped configs, and then AdamW gets `model.parameters()` as its one group, :74), `experiments.config.retrieval` (recall@K, median
+rank and MRR of the validation pairs in `self.retrieval`, retrieval.py; no shipped config sets it).
 """
 import os
 import time
@@ -128,6 +129,10 @@ class ClassifierExperiment:
         self.early_stopper = EarlyStopper(patience=self.config.base.patience, delta=0, trace_func=logger.warning, save=self._lead)
         self.writer = _summary_writer(self.config.base.tensorboard_export_dir) if self._lead else _NullWriter()
         self._sync = None
+        # retrieval metrics at validation (additive, retrieval.py): null / absent = validate() is what it was
+        from ..retrieval import parse_config
+        self._retrieval_kw = parse_config(_get(config, "experiments.config.retrieval", None))
+        self.retrieval = None
 
     # ---- data parallelism (additive: the reference is single-process) --------------------------------------------
     def _towers(self):
@@ -240,6 +245,10 @@ class ClassifierExperiment:
         self.model.eval()
         metric_names = self.config.experiments.config.metrics
         loss_list, targets, preds = [], {}, {}
+        retr = None
+        if self._retrieval_kw is not None:
+            from ..retrieval import RetrievalMetrics
+            retr = RetrievalMetrics(comm=self.comm, **self._retrieval_kw)
         with torch.no_grad():
             prompt_emb = {}
             for name, tokens in self._prompt_token_sets().items():
@@ -251,6 +260,8 @@ class ClassifierExperiment:
                 outputs = self.model(batch)                      # :166 (no `validation` flag: MMGCLIPLoss keeps its second text pass)
                 loss, _ = self.criterion(**outputs)              # :169 the configured criterion, t2t term included
                 loss_list.append(loss.item())
+                if retr is not None:
+                    retr.update(outputs["image_embeddings"], outputs["text_embeddings"], batch["text_tokens"]["input_ids"])
                 labels = batch["prompt_labels"]
                 scale = outputs["logit_scale"].reshape(1).float().contiguous()
                 for name, te in prompt_emb.items():
@@ -277,6 +288,12 @@ class ClassifierExperiment:
         mean_auc = float(np.mean(list(aucs.values()))) if len(aucs) > 1 else -1
         if len(aucs) > 1:
             self.writer.add_scalar('auc/val/average', mean_auc, self.current_epoch + 1)
+        if retr is not None:                  # beside the 5-tuple, never in it: early stopping does not see it
+            self.retrieval = retr.compute()
+            for name, value in self.retrieval.items():
+                self.writer.add_scalar(f'retrieval/val/{name}', value, self.current_epoch + 1)
+            if self._lead:
+                logger.info("retrieval/val " + " | ".join(f"{k} {v:.4g}" for k, v in self.retrieval.items()))
         return (epoch_loss, aucs.get("malig", -1), aucs.get("shapes", -1), aucs.get("birads", -1),
                 mean_auc if len(metric_names) > 1 else -1)
 

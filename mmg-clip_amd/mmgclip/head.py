@@ -1,6 +1,6 @@
 """Host side of the contrastive heads: autograd wrappers over the fp32 gfx950 kernels of csrc/clip_head.hip (CLIP),
 csrc/averaged_head.hip (AveragedMedicalCLIP) and csrc/sigmoid_head.hip (sigmoid pairwise), which share the tile skeleton of
-csrc/clip_tile.h.
+csrc/clip_tile.h, and the backend of the retrieval ranks at validation (csrc/retrieval_head.hip, same skeleton; mmgclip/retrieval.py).
 
 Reference arithmetic (path:line in the reference tree):
     mmgclip/networks/mmgclip_model.py:128-136  normalise, exp(logit_scale), two logit matmuls
@@ -416,6 +416,24 @@ class FusedSigmoidLoss(torch.autograd.Function):
 def fused_sigmoid_loss(image_embeddings, text_embeddings, logit_scale, logit_bias, positives="diagonal", threshold=0.65, comm=None):
     """Sigmoid pairwise loss on normalised embeddings -> (loss, labels_of_local_rows); `logit_scale` is the exponentiated scale."""
     return FusedSigmoidLoss.apply(image_embeddings, text_embeddings, logit_scale, logit_bias, positives, float(threshold), comm)
+
+
+class _HipRetrievalBackend:
+    """The product arithmetic of the retrieval metrics (mmgclip/retrieval.py): the one entry point of csrc/retrieval_head.hip.  As with
+    `_HipHeadBackend`, no product signature selects anything else; tests/test_retrieval_cpu.py replaces this module attribute in its
+    worker processes (gloo, CPU).  `row_key` / `col_label` None = the diagonal at `diag_off`."""
+
+    @staticmethod
+    def rank(x_loc, y_all, row_key, col_label, diag_off):
+        """(best fp32, n_pos, n_gt, n_eq int32), each [n_loc]: the best positive score of every local query and the negatives of
+        the gallery above / at it.  No autograd, no [n_loc,N] allocation."""
+        _hip.require_gpu(x_loc, y_all, row_key, col_label)
+        n_loc, D = x_loc.shape
+        best = torch.empty(n_loc, device=x_loc.device, dtype=torch.float32)
+        n_pos, n_gt, n_eq = (torch.empty(n_loc, device=x_loc.device, dtype=torch.int32) for _ in range(3))
+        call("mmg_retrieval_rows_rank", ptr(x_loc), ptr(y_all), ptr(row_key), ptr(col_label), n_loc, y_all.shape[0], D, diag_off,
+             ptr(best), ptr(n_pos), ptr(n_gt), ptr(n_eq), stream())
+        return best, n_pos, n_gt, n_eq
 
 
 class ClusterMeanCols(torch.autograd.Function):
