@@ -449,6 +449,25 @@ int mmg_sigmoid_rows_bwd(const float* X, const float* Y, const float* scale, con
 int mmg_retrieval_rows_rank(const float* X, const float* Y, const long long* row_key, const long long* col_label, int n_loc, int N,
                             int D, int diag_off, float* best, int* n_pos, int* n_gt, int* n_eq, mmg_stream_t stream);
 
+/* Zero-shot AUROC with bootstrap replicates as exact integer pair counts (validation / evaluation; csrc/auroc_head.hip).
+ *   U2[b] = sum_{i<P} sum_{j<Nn} w_pos[b][i] * w_neg[b][j] * g(s_pos[i], s_neg[j]),  g = 2 [s+ > s-] + [s+ == s-],
+ *   AUROC_b = U2[b] / (2 * sum_i w_pos[b][i] * sum_j w_neg[b][j])   (the host divides; weights all 1 = the point estimate).
+ * s_pos [P], s_neg [Nn] fp32, finite normal numbers or zero (NaN and denormals are not defined); w_pos [B][ldw_pos], w_neg [B][ldw_neg]
+ * int8 in 0..127, replicate-major; ldw_* a multiple of 16 and at least P / Nn (so at least the width padded to 16); the columns
+ * Nn .. ldw_neg-1 of w_neg hold 0; s_neg and w_neg 16-byte aligned.  partial: int64 [ceil(P/32)][B], every element written; the host
+ * sums the row blocks in int64.  v_mfma_i32_32x32x32_i8, int32 accumulators: the caller guarantees 2 * max_b sum_j w_neg[b][j] < 2^31.
+ * One owner per (row block, replicate), a fixed integer tree, no atomics, no memset: bit-identical from run to run and however the
+ * positives are split over launches.  Rows beyond P and columns beyond Nn add exactly nothing. */
+int mmg_auroc_pairs(const float* s_pos, const float* s_neg, const signed char* w_pos, int ldw_pos, const signed char* w_neg,
+                    int ldw_neg, int P, int Nn, int B, long long* partial, mmg_stream_t stream);
+
+/* Bootstrap multiplicities: w[b - b0][t] (int8, row stride ldw, a multiple of 16 and >= n; w 16-byte aligned) = how many of replicate
+ * b's n draws landed on sample t, for b = b0 .. b0+B-1 (B <= 65535); columns n .. ldw-1 are written as 0.  Draw t' of replicate b is
+ *   idx = (mmg_drop_bits(t', mmg_drop_key_bh(mmg_drop_key(seed, 0x200), b)) * n) >> 32      (the hash of csrc/dropout.h)
+ * - a pure function of (seed, b, t'); the multiply-high's bias is below n / 2^32 per value.  Integer LDS counters, no scratch.  A count
+ * above 127 does not wrap: it is written as -128 and the host raises on any negative weight. */
+int mmg_bootstrap_weights(unsigned long long seed, int n, int b0, int B, signed char* w, int ldw, mmg_stream_t stream);
+
 /* ---- fp8 (OCP e4m3) forward GEMM path: BASELINE config C5 "ConvNeXt-base fp8 MFMA path" ---------------------------------
  * The reference has no reduced-precision path (its towers run torch fp32, mmgclip/networks/encoder.py:53,156); these replace
  * the same nn.Linear forwards of torchvision's CNBlock as mmg_gemm_nt_bf16 does, on v_mfma_f32_16x16x128_f8f6f4 (twice the

@@ -114,9 +114,27 @@ class Evaluator:
         _, _, sims = head.rows_forward(ie, te, scale.contiguous(), 0, True)
         return sims.cpu().numpy()
 
-    def zeroshot_label_prompt(self, image_embeddings, label_names, classes_dict, key, use_logits=True, n_iterations=1000):
+    def bootstrap_ci_config(self):
+        """`config.dataset.eval.bootstrap_ci` -> the `ci` / `seed` keywords of `zeroshot_label_prompt`: "host" | "device", or a mapping
+        with `ci` and `seed`; absent = the method's defaults."""
+        from .networks.mmgclip_model import _get
+        node = _get(self.config, "dataset.eval.bootstrap_ci", None)
+        if node is None:
+            return {}
+        node = {"ci": node} if isinstance(node, str) else dict(node)
+        unknown = set(node) - {"ci", "seed"}
+        if unknown:
+            raise ValueError(f"dataset.eval.bootstrap_ci: unknown keys {sorted(unknown)}")
+        return node
+
+    def zeroshot_label_prompt(self, image_embeddings, label_names, classes_dict, key, use_logits=True, n_iterations=1000, ci="host", seed=0):
+        """`ci`: "host" (the reference's loop below, unseeded) or "device" (zeroshot_auroc.ZeroShotAUROC: every prompt's `auc` and
+        the interval of a two-prompt task as exact pair counts from the kernel, reproducible from `seed`).  `evaluate_experiment`
+        passes what `config.dataset.eval.bootstrap_ci` says when that key is present."""
         from scipy.special import softmax
         from sklearn import metrics
+        if ci not in ("host", "device"):
+            raise ValueError(f'ci must be "host" or "device", got {ci!r}')
         logger.info(f"Evaluating zero-shot prompt configuration for {key}.")
         label_names = [process_class_list([label[key]]) for label in label_names]
         prompts = label_prompts(key, classes_dict)
@@ -125,9 +143,20 @@ class Evaluator:
         y_pred = np.argmax(similarities, axis=-1)
         results = {}
         for idx, value in enumerate(prompts):
-            results[value] = {'auc': metrics.roc_auc_score(y_true == idx, similarities[:, idx]),
+            results[value] = {'auc': metrics.roc_auc_score(y_true == idx, similarities[:, idx]) if ci == "host" else None,   # (device: below)
                               'accuracy': np.mean((y_pred == idx) == (y_true == idx))}
-        if len(prompts) == 2:                                   # bootstrap CI of the positive class's AUROC (:417-468)
+        if ci == "device":
+            from .zeroshot_auroc import ZeroShotAUROC
+            boot = len(prompts) == 2
+            zs = ZeroShotAUROC(n_bootstrap=n_iterations if boot else 0, seed=seed)
+            zs.update(key, torch.as_tensor(similarities, dtype=torch.float32, device=self.device), torch.as_tensor(y_true),
+                      list(range(len(prompts))))
+            classes = zs.compute()[key]["classes"]
+            for idx, value in enumerate(prompts):
+                results[value]['auc'] = classes[idx]['auc']
+            if boot:
+                results['auc_ci_mean'], results['auc_ci_lower'], results['auc_ci_higher'] = (classes[1][k] for k in ("ci_mean", "ci_lower", "ci_upper"))
+        elif len(prompts) == 2:                                 # bootstrap CI of the positive class's AUROC (:417-468)
             pos = similarities[:, 1]
             scores = []
             for _ in range(n_iterations):
@@ -192,7 +221,7 @@ class Evaluator:
             if "zeroshot_label_prompt" in methods:
                 create_directory_if_not_exists(os.path.join(out_dir, 'zeroshot_label_prompt'))
                 results = self.zeroshot_label_prompt(image_embeddings=image_embeddings, label_names=labels, classes_dict=classes_dict,
-                                                     key=enum_class_name)
+                                                     key=enum_class_name, **self.bootstrap_ci_config())
                 logger.info(f"Results From zero-shot label prompt evaluation...\n{results}\n")
                 experiments_results.append(results)
             if "confustion_matrix" in methods:       # (sic: the reference's spelling of the config value)

@@ -11,7 +11,9 @@ Additive options: `distributed.global_loss`, `optimizer.config.fused` (FusedAdam
 NaN / Inf gradient; the reference goes from backward straight to step, :115-118, and so does a shipped config),
 `optimizer.config.layer_decay` / `no_decay_1d` / `image_lr_mult` / `text_lr_mult` (param groups, optim_groups.py; absent from the
 shipped configs, and then AdamW gets `model.parameters()` as its one group, :74), `experiments.config.retrieval` (recall@K, median
-rank and MRR of the validation pairs in `self.retrieval`, retrieval.py; no shipped config sets it).
+rank and MRR of the validation pairs in `self.retrieval`, retrieval.py; no shipped config sets it), `experiments.config.zeroshot_auroc`
+(the prompt AUROCs once more, global over the ranks and with seeded bootstrap intervals, in `self.zeroshot`, zeroshot_auroc.py; no
+shipped config sets it, and the 5-tuple is what it was either way).
 """
 import os
 import time
@@ -133,6 +135,12 @@ class ClassifierExperiment:
         from ..retrieval import parse_config
         self._retrieval_kw = parse_config(_get(config, "experiments.config.retrieval", None))
         self.retrieval = None
+        # global zero-shot AUROC with bootstrap intervals (additive, zeroshot_auroc.py): null / absent = nothing of it is imported
+        self._zeroshot_kw = None
+        if _get(config, "experiments.config.zeroshot_auroc", None) is not None:
+            from ..zeroshot_auroc import parse_config as parse_zeroshot
+            self._zeroshot_kw = parse_zeroshot(_get(config, "experiments.config.zeroshot_auroc", None))
+        self.zeroshot = None
 
     # ---- data parallelism (additive: the reference is single-process) --------------------------------------------
     def _towers(self):
@@ -249,6 +257,10 @@ class ClassifierExperiment:
         if self._retrieval_kw is not None:
             from ..retrieval import RetrievalMetrics
             retr = RetrievalMetrics(comm=self.comm, **self._retrieval_kw)
+        zs = None
+        if self._zeroshot_kw is not None:
+            from ..zeroshot_auroc import ZeroShotAUROC
+            zs = ZeroShotAUROC(comm=self.comm, **self._zeroshot_kw)
         with torch.no_grad():
             prompt_emb = {}
             for name, tokens in self._prompt_token_sets().items():
@@ -268,11 +280,16 @@ class ClassifierExperiment:
                     _, _, sims = head.rows_forward(outputs["image_embeddings"].contiguous(), te, scale, 0, True)   # [n,k]
                     preds[name].append(sims.cpu().numpy())
                     if name == "malig":         # int (exam-report dataset) or the enum member's name (image-label dataset): :179-185
-                        targets[name].extend(_label_value(l["BenignMalignantDatasetLabels"], BENIGN_MALIGNANT) for l in labels)
+                        batch_targets = [_label_value(l["BenignMalignantDatasetLabels"], BENIGN_MALIGNANT) for l in labels]
                     elif name == "shapes":      # :199-202
-                        targets[name].extend(_label_value(l["MassShapeLabels"], MASS_SHAPES) for l in labels)
+                        batch_targets = [_label_value(l["MassShapeLabels"], MASS_SHAPES) for l in labels]
                     else:
-                        targets[name].extend(-1 if l["BIRADS"] == "unknown" else int(l["BIRADS"]) for l in labels)
+                        batch_targets = [-1 if l["BIRADS"] == "unknown" else int(l["BIRADS"]) for l in labels]
+                    targets[name].extend(batch_targets)
+                    if zs is not None:          # the same scores, kept on the device; classes as the loop below takes them
+                        k = sims.shape[1]
+                        values = [1] if name == "malig" else [i - (1 if name == "birads" else 0) for i in range(k)]
+                        zs.update(name, sims[:, :len(values)], torch.tensor(batch_targets, dtype=torch.int64, device=sims.device), values)
         epoch_loss = float(np.mean(loss_list)) if loss_list else float("nan")
         self.writer.add_scalar('loss/val', epoch_loss, self.current_epoch + 1)
         aucs = {}
@@ -294,6 +311,18 @@ class ClassifierExperiment:
                 self.writer.add_scalar(f'retrieval/val/{name}', value, self.current_epoch + 1)
             if self._lead:
                 logger.info("retrieval/val " + " | ".join(f"{k} {v:.4g}" for k, v in self.retrieval.items()))
+        # beside the 5-tuple as well: global over the ranks, with intervals.  compute() is collective: in a data-parallel run every
+        # rank must have fed the same tasks (a rank whose validation loader is empty cannot take part, as with the retrieval metrics)
+        if zs is not None and zs.has_data:
+            self.zeroshot = zs.compute()
+            for name, task in self.zeroshot.items():
+                for key in ("auc", "ci_lower", "ci_upper"):
+                    if key in task:
+                        self.writer.add_scalar(f'auc_global/val/{name}' + ("" if key == "auc" else f"_{key}"), task[key], self.current_epoch + 1)
+            if self._lead:
+                logger.info("auc_global/val " + " | ".join(
+                    f"{n} {t['auc']:.4f}" + (f" [{t['ci_lower']:.4f}, {t['ci_upper']:.4f}]" if "ci_lower" in t else "")
+                    for n, t in self.zeroshot.items()))
         return (epoch_loss, aucs.get("malig", -1), aucs.get("shapes", -1), aucs.get("birads", -1),
                 mean_auc if len(metric_names) > 1 else -1)
 

@@ -436,6 +436,41 @@ class _HipRetrievalBackend:
         return best, n_pos, n_gt, n_eq
 
 
+class _HipAurocBackend:
+    """The product arithmetic of the zero-shot AUROC with bootstrap replicates (mmgclip/zeroshot_auroc.py): the two entry points of
+    csrc/auroc_head.hip.  As with `_HipRetrievalBackend`, no product signature selects anything else; tests/test_auroc_cpu.py replaces
+    this module attribute.  Weights are int8 [B, ld], replicate-major, ld a multiple of 16 with zeros in the padding."""
+
+    @staticmethod
+    def bootstrap_weights(seed, n, b0, B, device=None):
+        """int8 [B, ceil16(n)]: how many of replicate b's n draws landed on sample t, b = b0 .. b0+B-1; padding columns 0.  A count
+        above 127 comes back as -128: the caller raises on any negative weight (one read-back for all its chunks)."""
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        w = torch.empty((B, (n + 15) // 16 * 16), device=device, dtype=torch.int8)
+        _hip.require_gpu(w)
+        call("mmg_bootstrap_weights", int(seed) & 0xFFFFFFFFFFFFFFFF, n, b0, B, ptr(w), w.shape[1], stream())
+        return w
+
+    @staticmethod
+    def pairs(s_pos, s_neg, w_pos, w_neg, neg_total=None):
+        """int64 [B]: U2_b = sum_ij w_pos[b,i] w_neg[b,j] (2 [s+_i > s-_j] + [s+_i == s-_j]), exact.  The int32 accumulator bound
+        2 max_b sum_j w_neg[b,j] < 2^31 is checked here: against `neg_total`, an upper bound of every replicate's negative weights
+        that the caller can prove (a bootstrap of N draws: N), or, without one, by a device reduction read back (torch widens the
+        int8 weights for it: a transient of 8 bytes per weight)."""
+        _hip.require_gpu(s_pos, s_neg, w_pos, w_neg)
+        s_pos, s_neg = _f32c(s_pos), _f32c(s_neg)
+        P, Nn, B = s_pos.shape[0], s_neg.shape[0], w_neg.shape[0]
+        if w_pos.dtype != torch.int8 or w_neg.dtype != torch.int8 or w_pos.shape[0] != B or not (w_pos.is_contiguous() and w_neg.is_contiguous()):
+            raise ValueError("weights must be contiguous int8 [B, ld] with one row per replicate in both matrices")
+        heaviest = int(w_neg.sum(dim=1, dtype=torch.int64).max()) if neg_total is None else int(neg_total)
+        if 2 * heaviest >= 2 ** 31:
+            raise ValueError(f"a replicate's negative weights sum to {heaviest}: 2 * that must stay below 2^31 (int32 accumulators)")
+        partial = torch.empty(((P + 31) // 32, B), device=s_pos.device, dtype=torch.int64)
+        call("mmg_auroc_pairs", ptr(s_pos), ptr(s_neg), ptr(w_pos), w_pos.shape[1], ptr(w_neg), w_neg.shape[1], P, Nn, B, ptr(partial),
+             stream())
+        return partial.sum(dim=0)
+
+
 class ClusterMeanCols(torch.autograd.Function):
     """[n,N] logits -> [n,k] per-cluster column means (losses.py:164-186) and the matching gradient."""
 
