@@ -293,6 +293,16 @@ int mmg_dwconv7_wgrad(const void* x, const void* dy, float* dw, float* dbias, in
 
 /* ---- fused ConvNeXt block MLP (C in {96,128,192,256,384,512}) ---------------------------------------------------------- */
 
+/* What mmg_cnblock_mlp_fwd (op 0), mmg_cnblock_mlp_bwd (op 1) or mmg_cnblock_bwdw (op 2) would launch for M rows of width C, as text:
+ * the kernel instantiation as mmg_last_kernel() spells it (op 2: both launches, "cnblock_bwdw_kernel<..> + <..>"), then
+ * " grid=G block=T lds=B nt=0|1 tiles=N" (workgroups, threads - op 2: "block=(T1,T2)" -, dynamic LDS bytes, nt = the 4C-wide outputs are
+ * stored past L2, N = tiles walked).  save (op 0 only): the forward saves hpre and the row statistics; ln (op 1 only): ln_dw / ln_db are
+ * given; cus: CU count the plan is made for, 0 = the current device's.  MMG_MLP_FWD_RES / MMG_MLP_NT_STORE / MMG_BWDW_VAR / MMG_BWDW_HTO /
+ * MMG_BWDW_W12 are honoured as by a launch.  A shape the entry point would reject gives "" and sets mmg_last_error() to that entry point's
+ * message.  The string belongs to the calling thread and is valid until its next call; no GPU is needed when cus != 0.  No reference
+ * counterpart (diagnostics; tests/test_cnblock_plan_cpu.py pins kernel selection with it).  Additive entry point: mmg_abi_version() stays 5. */
+const char* mmg_cnblock_plan(int op, long long M, int C, int save, int ln, int cus);
+
 /* Number of bf16 elements of the packed weight image (8C^2 forward / backward=2, 12C^2 backward=1); 0 when C is unsupported. */
 long long mmg_cnblock_packed_elems(int C, int backward);
 /* Pack W1 fp32 [4C,C], W2 fp32 [C,4C] (torchvision CNBlock.block[3] / block[5]) into the per-chunk LDS images the fused

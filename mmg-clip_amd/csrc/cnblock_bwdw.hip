@@ -26,13 +26,13 @@
 //     through an fp32 LDS tile in a row-per-8-lanes layout with 16-byte global accesses.
 // LayerNorm is folded: the row images hold xhat = (d - mean) rstd in bf16, gamma_ln multiplies the packed W1 of the first product and
 // beta enters through the bias b1' = b1 + W1 beta; the weight gradient is un-folded at the end (dW1 = gamma (dh^T xhat) + db1 beta^T).
-#include "common.h"
-#include <stdlib.h>
+// Host side: cnblock_plan.h / cnblock_plan.hip hold the argument checks, the knobs and the plan of both launches; the doors below launch what it names.
+#include "cnblock_plan.h"
 
 
 template <int C> struct BwCfg {
     static constexpr int H4 = 4 * C;               // hidden width
-    static constexpr int R = 64;                   // rows per tile
+    static constexpr int R = cn_bw_cfg(C).R;       // rows per tile (cnblock_plan.h: the host-side plan reads R, LDS and PK_TOTAL too)
     static constexpr int KS = C / 32;              // k-steps of the C-deep products (3)
     static constexpr int CT = C / 16;              // 16-column tiles of a C-wide result (6)
     static constexpr int KG = C / 8;               // 16-byte columns of a row image (12)
@@ -43,11 +43,13 @@ template <int C> struct BwCfg {
     static constexpr int DHIMG = (R / 16) * 4 * NP1 * 8;
     static constexpr int OFF_W1 = 0, OFF_X = W1IMG, OFF_DY = OFF_X + ROWIMG, OFF_DH = OFF_DY + ROWIMG;
     static constexpr int OFF_LNW = OFF_DH + DHIMG, OFF_B1 = OFF_LNW + C * 4, OFF_STAT = OFF_B1 + H4 * 4;
-    static constexpr int LDS = OFF_STAT + 2 * R * 2 * 4;
+    static constexpr int LDS = cn_bw_cfg(C).LDS;
+    static_assert(OFF_STAT + 2 * R * 2 * 4 == LDS, "cn_bw_cfg: the layout above fills exactly the LDS the plan asks for");
     // packed weight buffer (bf16 elements): [W1 LDS image][W1 gamma fragments][gamma_ls W2^T fragments]
     static constexpr long PK_W1IMG = (long)KG * NP1 * 8;
     static constexpr long PK_FRAGS = (long)(H4 / 16) * KS * 64 * 8;
-    static constexpr long PK_TOTAL = PK_W1IMG + 2 * PK_FRAGS;
+    static constexpr long PK_TOTAL = cn_bw_cfg(C).PK_TOTAL;
+    static_assert(PK_W1IMG + 2 * PK_FRAGS == PK_TOTAL, "cn_bw_cfg: the packed buffer is the W1 image and two fragment sets");
     static constexpr int DLP = C + 4;              // pitch (floats) of the fp32 d LN-out tile: +4 makes the LayerNorm-backward row reads conflict-free
     static_assert(R * DLP * 4 <= DHIMG, "the fp32 d LN-out tile aliases the dh image");
     static_assert(LDS <= 160 * 1024, "LDS budget");
@@ -681,17 +683,15 @@ __global__ __launch_bounds__(256) void cnblock_bwdw_pack_kernel(const BwPack a) 
     }
 }
 
-#define BW_DEFAULT_VAR 2
-#define BW_DEFAULT_HTO 1
-static int bw_cu_count() { return mmg_cu_count_cached(); }
-
-MMG_API int mmg_cnblock_bwdw_supported(int C) { return C == 96 ? 1 : 0; }
-MMG_API long long mmg_cnblock_bwdw_packed_elems(int C) { return C == 96 ? (long long)BwCfg<96>::PK_TOTAL : 0; }
+// ---- the doors: validate (cnblock_plan.hip, before any HIP call), plan, launch what the plan names ------------------------------------------
+MMG_API int mmg_cnblock_bwdw_supported(int C) { return cn_bwdw_supported(C) ? 1 : 0; }
+MMG_API long long mmg_cnblock_bwdw_packed_elems(int C) { return cn_bwdw_supported(C) ? (long long)cn_bw_cfg(C).PK_TOTAL : 0; }
 
 MMG_API int mmg_cnblock_bwdw_pack(const float* w1, const float* w2, const float* ln_w, const float* ln_b, const float* layer_scale,
                                   const float* b1, void* packed, float* b1f, int C, hipStream_t stream) {
-    MMG_CHECK_ARG(C == 96, "mmg_cnblock_bwdw_pack: C=%d is not supported (96)", C);
-    MMG_CHECK_ARG(w1 && w2 && ln_w && ln_b && layer_scale && b1 && packed && b1f, "mmg_cnblock_bwdw_pack: null pointer");
+    CnArgs c = {};
+    c.C = C; c.operands = w1 && w2 && ln_w && ln_b && layer_scale && b1 && packed && b1f;
+    if (cn_check(CN_BWDW_PACK, c)) return 1;
     BwPack a{w1, w2, ln_w, ln_b, layer_scale, b1, (bf16_t*)packed, b1f, C};
     hipLaunchKernelGGL(cnblock_bwdw_pack_kernel<96>, dim3(128), dim3(256), 0, stream, a);
     MMG_LAUNCH_CHECK("mmg_cnblock_bwdw_pack");
@@ -701,50 +701,28 @@ MMG_API int mmg_cnblock_bwdw_pack(const float* w1, const float* w2, const float*
 MMG_API int mmg_cnblock_bwdw(const void* dy, const void* xd, const float* ln_w, const float* ln_b, float eps, const void* packed,
                              const float* b1f, void* dd, float* dW1, float* db1, float* dW2raw, float* db2raw, float* ln_dw,
                              float* ln_db, long long M, int C, hipStream_t stream) {
-    MMG_CHECK_ARG(C == 96, "mmg_cnblock_bwdw: C=%d is not supported (96)", C);
-    MMG_CHECK_ARG(M > 0 && M % BwCfg<96>::R == 0, "mmg_cnblock_bwdw: M=%lld must be a positive multiple of %d", M, BwCfg<96>::R);
-    MMG_CHECK_ARG(M * 96 * 2 < (1LL << 32), "mmg_cnblock_bwdw: M=%lld rows exceed the 4 GiB buffer range of one launch", M);
-    MMG_CHECK_ARG(dy && xd && ln_w && ln_b && packed && b1f && dd && dW1 && db1 && dW2raw && db2raw && ln_dw && ln_db,
-                  "mmg_cnblock_bwdw: null pointer");
+    CnArgs c = {};
+    c.M = M; c.C = C; c.operands = dy && xd && ln_w && ln_b && packed && b1f && dd && dW1 && db1 && dW2raw && db2raw && ln_dw && ln_db;
+    if (cn_check(CN_BWDW, c)) return 1;
+    const CnPlan pl = cn_plan(CN_BWDW, M, C, 0, 0, mmg_cu_count_cached(), cn_knobs());
     BwArgs a;
     a.dy = (const bf16_t*)dy; a.xd = (const bf16_t*)xd; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps;
     a.packed = (const bf16_t*)packed; a.b1f = b1f; a.dd = (bf16_t*)dd;
     a.dW1 = dW1; a.db1 = db1; a.dW2raw = dW2raw; a.db2raw = db2raw; a.ln_dw = ln_dw; a.ln_db = ln_db;
-    a.M = M; a.ntiles = (int)(M / BwCfg<96>::R);
-    const int cap = bw_cu_count();
-    const int grid = a.ntiles < cap ? a.ntiles : cap;
-    // launch 1 with 12 waves (three per SIMD, 168 registers): same-box A/B at 16.8 M rows, two runs each: 13.10 / 13.15 ms against
-    // 12.94 / 13.09 with 8 waves - the launch is bound by VALU issue (GELU), not by latency, so the third wave buys nothing.  Off.
-    // (MMG_BWDW_W12: read per call like the other knobs here, so that a test reaches <96, 1, 12, 0> in the process that ran the default)
-    const char* ew = getenv("MMG_BWDW_W12");
-    const int w12 = ew ? atoi(ew) : 0;
-    // schedule of launch 1 (see the kernel's VAR comment); MMG_BWDW_VAR = 0 / 1 / 2 for same-process A/B runs (tools/bwdw_bench.py)
-    const char* ev = getenv("MMG_BWDW_VAR");
-    const int var = ev ? atoi(ev) : BW_DEFAULT_VAR;
-    const char* eh = getenv("MMG_BWDW_HTO");                 // (read per call: same-process A/B runs, tools/bwdw_bench.py)
-    const int hto = eh ? atoi(eh) : BW_DEFAULT_HTO;
-    typedef BwCfg<96> Cfg;
-    // both launches by name, as the branches below choose them
-    MMG_NOTE_KERNEL("cnblock_bwdw_kernel<96, 1, %d, %d> + <96, 2, 8, %d>", w12 ? 12 : 8, w12 ? 0 : (var == 2 ? 2 : (var == 1 ? 1 : 0)), hto ? 1 : 0);
-    if (w12) {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 12, 0>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 12, 0>), dim3(grid), dim3(768), Cfg::LDS, stream, a);
-    } else if (var == 2) {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 8, 2>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 8, 2>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
-    } else if (var == 1) {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 8, 1>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 8, 1>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
-    } else {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 1, 8, 0>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 1, 8, 0>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
-    }
-    if (hto) {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 2, 8, 1>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 2, 8, 1>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
-    } else {
-        mmg_allow_lds(cnblock_bwdw_kernel<96, 2, 8, 0>, Cfg::LDS);
-        hipLaunchKernelGGL((cnblock_bwdw_kernel<96, 2, 8, 0>), dim3(grid), dim3(512), Cfg::LDS, stream, a);
+    a.M = M; a.ntiles = pl.ntiles;
+    MMG_NOTE_KERNEL("%s", cn_plan_name(pl));
+    const int launch[2][2] = {{pl.kernel, pl.block}, {pl.kernel2, pl.block2}};
+    for (int i = 0; i < 2; ++i) {
+        switch (launch[i][0]) {
+#define KW(C, MODE, NW, VAR)                                                                                                    \
+    case CK_bwdw_##C##_##MODE##_##NW##_##VAR:                                                                                   \
+        mmg_allow_lds(cnblock_bwdw_kernel<C, MODE, NW, VAR>, pl.lds);                                                           \
+        hipLaunchKernelGGL((cnblock_bwdw_kernel<C, MODE, NW, VAR>), dim3(pl.grid), dim3(launch[i][1]), pl.lds, stream, a);      \
+        break;
+            CN_BWDW_KERNELS(KW)
+#undef KW
+            default: mmg_set_error("mmg_cnblock_bwdw: no kernel for plan %d", launch[i][0]); return 1;
+        }
     }
     MMG_LAUNCH_CHECK("mmg_cnblock_bwdw");
     return 0;

@@ -20,8 +20,8 @@
 // The bound is the fp32 VALU (erf-GELU: the 11-operation polynomial form of common.h, gelu_bf16 - its result is rounded to bf16
 // right away; still ~2x the MFMA time at C=96), then HBM; the
 // backward (cnblock_mlp_bwd_kernel below) recomputes the hidden row and is bound by its 4C-wide stores.
-#include "common.h"
-#include <stdlib.h>
+// Host side: cnblock_plan.h / cnblock_plan.hip hold the argument checks, the knobs and the plan of every launch; the doors below launch what it names.
+#include "cnblock_plan.h"
 
 
 struct MlpFwd {
@@ -46,17 +46,17 @@ __device__ __forceinline__ void mlp_glds16(const void* gsrc, void* lds_wave_base
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// Work split per width.  Up to C = 256 a wave owns 32 rows (two 16-row MFMA tiles share every weight fragment read); at C = 384
-// the per-row state (C/4 operand + C/4 accumulator registers per tile) only leaves room for one tile per wave, so the
-// workgroup is 8 waves of 16 rows (one workgroup per CU) and the kernel is LDS-read bound (one fragment read per MFMA).
+// Work split per width: the constants live in cnblock_plan.h (cn_cfg), where the host-side plan reads them too.
 template <int C> struct MlpCfg {
-    static constexpr int NC = (C <= 128) ? 64 : 32;                     // hidden columns per streamed chunk
-    static constexpr int MT = (C <= 256) ? 2 : 1;                       // 16-row tiles per wave
-    static constexpr int WAVES = (C <= 256) ? 4 : 8;
+    static constexpr CnCfg K = cn_cfg(C);
+    static constexpr int NC = K.NC;                                     // hidden columns per streamed chunk
+    static constexpr int MT = K.MT;                                     // 16-row tiles per wave
+    static constexpr int WAVES = K.WAVES;
     static constexpr int THREADS = WAVES * 64;
-    static constexpr int BM = WAVES * 16 * MT;                          // rows per workgroup tile
-    static constexpr int WGS = (C <= 96) ? 3 : (C <= 192 ? 2 : 1);      // forward workgroups per CU (registers / LDS)
-    static constexpr int WGS_BWD = (C <= 192) ? 2 : 1;
+    static constexpr int BM = K.BM;                                     // rows per workgroup tile
+    static constexpr int WGS = K.WGS;                                   // forward workgroups per CU (registers / LDS)
+    static constexpr int WGS_BWD = K.WGS_BWD;
+    static_assert(BM == WAVES * 16 * MT && BM == 128, "cn_cfg: a workgroup tile is its waves' 16-row tiles, 128 rows at every width");
 };
 
 // ---- weight packing --------------------------------------------------------------------------------------------------
@@ -658,95 +658,19 @@ __global__ __launch_bounds__(MlpCfg<C>::THREADS, MlpCfg<C>::WGS_BWD) void cnbloc
     }
 }
 
-#define MLP_FWD_RES_DEFAULT 12
-static int mlp_cu_count() { return mmg_cu_count_cached(); }
-
-// The backward's 4C-wide outputs (g, dh) beyond the 256 MiB Infinity Cache are consumed much later by the weight-gradient GEMMs:
-// stored past L2 (nontemporal) from C = 128 up.  Same-run A/B (profiles/r02_mlp_nt_store_ab.txt): backward -8...-17 % at C = 192,
-// -12 % at 384, no change at 96; the forward's saved pre-activation is 1-3 % SLOWER that way and keeps plain stores.
-// MMG_MLP_NT_STORE=0/1 forces it off/on everywhere (read per call: A/B runs).
-static int mlp_nt_store(long M, int C, bool backward) {
-    const char* e = getenv("MMG_MLP_NT_STORE");
-    if (e) return atoi(e) != 0;
-    return backward && C >= 128 && (size_t)M * 4 * C * 2 >= ((size_t)256 << 20);
-}
-
-template <int C, bool RECOMP>
-static int launch_mlp_bwd(MlpBwd p, hipStream_t stream) {
-    typedef MlpCfg<C> Cfg;
-    p.nt = mlp_nt_store(p.M, C, true);
-    const size_t lds = 2 * ((RECOMP ? 3 : 2) * Cfg::NC * C * 2) + (size_t)8 * C * sizeof(float);
-    p.ntiles = (int)((p.M + Cfg::BM - 1) / Cfg::BM);
-    const int cap = Cfg::WGS_BWD * mlp_cu_count();
-    const int grid = p.ntiles < cap ? p.ntiles : cap;
-    MMG_NOTE_KERNEL("cnblock_mlp_bwd_kernel<%d, %s, %s>", C, RECOMP ? "true" : "false", p.ln_dw ? "true" : "false");
-    if (p.ln_dw) {
-        mmg_allow_lds(cnblock_mlp_bwd_kernel<C, RECOMP, true>, lds);
-        hipLaunchKernelGGL((cnblock_mlp_bwd_kernel<C, RECOMP, true>), dim3(grid), dim3(Cfg::THREADS), lds, stream, p);
-    } else {
-        mmg_allow_lds(cnblock_mlp_bwd_kernel<C, RECOMP, false>, lds);
-        hipLaunchKernelGGL((cnblock_mlp_bwd_kernel<C, RECOMP, false>), dim3(grid), dim3(Cfg::THREADS), lds, stream, p);
-    }
-    MMG_LAUNCH_CHECK("mmg_cnblock_mlp_bwd");
-    return 0;
-}
-
-template <int C>
-static int launch_mlp_fwd(MlpFwd p, hipStream_t stream) {
-    typedef MlpCfg<C> Cfg;
-    p.nt = p.hpre ? mlp_nt_store(p.M, C, false) : 0;
-    const size_t lds = 2 * (2 * Cfg::NC * C * 2) + (size_t)8 * C * sizeof(float);
-    p.ntiles = (int)((p.M + Cfg::BM - 1) / Cfg::BM);
-    const int cap = Cfg::WGS * mlp_cu_count();
-    const int grid = p.ntiles < cap ? p.ntiles : cap;
-    if constexpr (C == 96) {
-        // resident weights (see the kernel): MMG_MLP_FWD_RES = waves per workgroup (8 / 12; 0 = the streaming form), read per call
-        const char* e = getenv("MMG_MLP_FWD_RES");
-        const int rw = e ? atoi(e) : MLP_FWD_RES_DEFAULT;
-        if (!p.hpre && (rw == 8 || rw == 12)) {
-            const size_t ldsr = (size_t)(4 * C / Cfg::NC) * (2 * Cfg::NC * C * 2) + (size_t)8 * C * sizeof(float);
-            p.ntiles = (int)((p.M + 16 * Cfg::MT - 1) / (16 * Cfg::MT));          // 32-row wave tiles
-            const int cus = mlp_cu_count();
-            const int gridr = (p.ntiles + rw - 1) / rw < cus ? (p.ntiles + rw - 1) / rw : cus;
-            MMG_NOTE_KERNEL("cnblock_mlp_fwd_kernel<%d, false, %d>", C, rw);
-            if (rw == 12) {
-                mmg_allow_lds(cnblock_mlp_fwd_kernel<C, false, 12>, ldsr);
-                hipLaunchKernelGGL((cnblock_mlp_fwd_kernel<C, false, 12>), dim3(gridr), dim3(768), ldsr, stream, p);
-            } else {
-                mmg_allow_lds(cnblock_mlp_fwd_kernel<C, false, 8>, ldsr);
-                hipLaunchKernelGGL((cnblock_mlp_fwd_kernel<C, false, 8>), dim3(gridr), dim3(512), ldsr, stream, p);
-            }
-            MMG_LAUNCH_CHECK("mmg_cnblock_mlp_fwd");
-            return 0;
-        }
-    }
-    MMG_NOTE_KERNEL("cnblock_mlp_fwd_kernel<%d, %s>", C, p.hpre ? "true" : "false");
-    if (p.hpre) {
-        mmg_allow_lds(cnblock_mlp_fwd_kernel<C, true>, lds);
-        hipLaunchKernelGGL((cnblock_mlp_fwd_kernel<C, true>), dim3(grid), dim3(Cfg::THREADS), lds, stream, p);
-    } else {
-        mmg_allow_lds(cnblock_mlp_fwd_kernel<C, false>, lds);
-        hipLaunchKernelGGL((cnblock_mlp_fwd_kernel<C, false>), dim3(grid), dim3(Cfg::THREADS), lds, stream, p);
-    }
-    MMG_LAUNCH_CHECK("mmg_cnblock_mlp_fwd");
-    return 0;
-}
-
-static bool mlp_supported(int C) { return C == 96 || C == 128 || C == 192 || C == 256 || C == 384 || C == 512; }
-
+// ---- the doors: validate (cnblock_plan.hip, before any HIP call), plan, launch what the plan names ------------------------------------------
 MMG_API long long mmg_cnblock_packed_elems(int C, int backward) {
-    if (!mlp_supported(C)) return 0;
+    if (!cn_mlp_supported(C)) return 0;
     return (long long)(backward == 1 ? 3 : 2) * 4 * C * C;
 }
 
 MMG_API int mmg_cnblock_pack_weights(const float* w1, const float* w2, const float* gamma, void* packed, int C, int backward,
                                      hipStream_t stream) {
-    MMG_CHECK_ARG(w1 && w2 && packed, "mmg_cnblock_pack_weights: null pointer");
-    MMG_CHECK_ARG(mlp_supported(C), "mmg_cnblock_pack_weights: C=%d not in {96,128,192,256,384,512}", C);
-    MMG_CHECK_ARG(backward >= 0 && backward <= 2, "mmg_cnblock_pack_weights: backward=%d not in {0,1,2}", backward);
-    MMG_CHECK_ARG(!backward || gamma, "mmg_cnblock_pack_weights: the backward image needs the layer scale");
+    CnArgs c = {};
+    c.C = C; c.operands = w1 && w2 && packed; c.backward = backward; c.gamma = gamma;
+    if (cn_check(CN_PACK, c)) return 1;
     PackArgs a{};
-    a.out = (bf16_t*)packed; a.C = C; a.NC = C <= 128 ? 64 : 32;      // = MlpCfg<C>::NC
+    a.out = (bf16_t*)packed; a.C = C; a.NC = cn_cfg(C).NC;
     a.part[0] = PackPart{w1, 0, nullptr, 0};                       // W1 rows n, K = c            (hidden = x W1^T)
     if (!backward) {
         a.parts = 2;
@@ -765,49 +689,54 @@ MMG_API int mmg_cnblock_pack_weights(const float* w1, const float* w2, const flo
     return 0;
 }
 
+#define MLP_LAUNCH(KERNEL)                                                                                  \
+    mmg_allow_lds(KERNEL, pl.lds);                                                                          \
+    hipLaunchKernelGGL((KERNEL), dim3(pl.grid), dim3(pl.block), pl.lds, stream, p);                         \
+    break;
+
 MMG_API int mmg_cnblock_mlp_fwd(const void* xd, const float* ln_w, const float* ln_b, float eps, const void* packed,
                                 const float* b1, const float* b2, const float* gamma, const void* residual, void* y,
                                 void* hpre, void* xln, void* gact, float* mean, float* rstd, int hpre_kind, long long M, int C, hipStream_t stream) {
-    MMG_CHECK_ARG(xd && ln_w && ln_b && packed && b1 && b2 && gamma && residual && y, "mmg_cnblock_mlp_fwd: null pointer");
-    MMG_CHECK_ARG(mlp_supported(C), "mmg_cnblock_mlp_fwd: C=%d not in {96,128,192,256,384,512}", C);
-    MMG_CHECK_ARG(M > 0 && M < (1LL << 36), "mmg_cnblock_mlp_fwd: bad M=%lld", M);
-    MMG_CHECK_ARG((mean == nullptr) == (hpre == nullptr) && (rstd == nullptr) == (hpre == nullptr),
-                  "mmg_cnblock_mlp_fwd: hpre, mean and rstd are saved together or not at all");
-    MMG_CHECK_ARG(!xln || hpre, "mmg_cnblock_mlp_fwd: xln is saved next to hpre only");
-    MMG_CHECK_ARG(!gact || hpre, "mmg_cnblock_mlp_fwd: gact is saved next to hpre only");
-    MlpFwd p{(const bf16_t*)xd, ln_w, ln_b, eps, (const bf16_t*)packed, b1, b2, gamma, (const bf16_t*)residual, (bf16_t*)y,
-             (bf16_t*)hpre, (bf16_t*)xln, mean, rstd, (long)M, 0, 0, (bf16_t*)gact, hpre_kind};
-    MMG_CHECK_ARG(hpre_kind == 0 || (hpre_kind == 1 && hpre && gact), "mmg_cnblock_mlp_fwd: hpre_kind=%d (1 = GELU' in place of the pre-activation) needs hpre and gact", hpre_kind);
-    switch (C) {
-        case 96: return launch_mlp_fwd<96>(p, stream);
-        case 128: return launch_mlp_fwd<128>(p, stream);
-        case 192: return launch_mlp_fwd<192>(p, stream);
-        case 256: return launch_mlp_fwd<256>(p, stream);
-        case 384: return launch_mlp_fwd<384>(p, stream);
-        default: return launch_mlp_fwd<512>(p, stream);
+    CnArgs c = {};
+    c.M = M; c.C = C; c.operands = xd && ln_w && ln_b && packed && b1 && b2 && gamma && residual && y;
+    c.hpre = hpre; c.xln = xln; c.gact = gact; c.mean = mean; c.rstd = rstd; c.hpre_kind = hpre_kind;
+    if (cn_check(CN_FWD, c)) return 1;
+    const CnPlan pl = cn_plan(CN_FWD, M, C, hpre != nullptr, 0, mmg_cu_count_cached(), cn_knobs());
+    const MlpFwd p{(const bf16_t*)xd, ln_w, ln_b, eps, (const bf16_t*)packed, b1, b2, gamma, (const bf16_t*)residual, (bf16_t*)y,
+                   (bf16_t*)hpre, (bf16_t*)xln, mean, rstd, (long)M, pl.ntiles, pl.nt, (bf16_t*)gact, hpre_kind};
+    MMG_NOTE_KERNEL("%s", cn_plan_name(pl));
+    switch (pl.kernel) {
+#define KF(C, SAVE) case CK_fwd_##C##_##SAVE: MLP_LAUNCH((cnblock_mlp_fwd_kernel<C, SAVE>))
+#define KR(C, RW) case CK_fwd_##C##_res##RW: MLP_LAUNCH((cnblock_mlp_fwd_kernel<C, false, RW>))
+        CN_FWD_KERNELS(KF, KR)
+#undef KF
+#undef KR
+        default: mmg_set_error("mmg_cnblock_mlp_fwd: no kernel for plan %d", pl.kernel); return 1;
     }
+    MMG_LAUNCH_CHECK("mmg_cnblock_mlp_fwd");
+    return 0;
 }
 
-// 1: hidden row recomputed (forward saves nothing 4C-wide); 2: needs the forward's saved pre-activation `hpre`; 0: unsupported
-MMG_API int mmg_cnblock_mlp_bwd_supported(int C) { return (C == 96 || C == 128 || C == 192) ? 1 : (C == 384 ? 2 : 0); }
+MMG_API int mmg_cnblock_mlp_bwd_supported(int C) { return cn_mlp_bwd_mode(C); }
 
 MMG_API int mmg_cnblock_mlp_bwd(const void* dy, const void* xd, const float* ln_w, const float* ln_b, float eps,
                                 const void* packed_bwd, const float* b1, const void* hpre, void* dh, void* g, void* xln,
                                 void* dxln, float* mean, float* rstd, float* ln_dw, float* ln_db, long long M, int C,
                                 hipStream_t stream) {
-    MMG_CHECK_ARG(dy && xd && ln_w && ln_b && packed_bwd && b1 && dh && g && xln && dxln && mean && rstd,
-                  "mmg_cnblock_mlp_bwd: null pointer");
-    const int mode = mmg_cnblock_mlp_bwd_supported(C);
-    MMG_CHECK_ARG(mode != 0, "mmg_cnblock_mlp_bwd: C=%d not in {96,128,192,384}", C);
-    MMG_CHECK_ARG((mode == 2) == (hpre != nullptr), "mmg_cnblock_mlp_bwd: hpre is required for C=384 and unused otherwise (C=%d)", C);
-    MMG_CHECK_ARG(M > 0 && M < (1LL << 36), "mmg_cnblock_mlp_bwd: bad M=%lld", M);
-    MMG_CHECK_ARG((ln_dw == nullptr) == (ln_db == nullptr), "mmg_cnblock_mlp_bwd: ln_dw and ln_db go together");
-    MlpBwd p{(const bf16_t*)dy, (const bf16_t*)xd, ln_w, ln_b, eps, (const bf16_t*)packed_bwd, b1, (bf16_t*)dh, (bf16_t*)g,
-             (bf16_t*)xln, (bf16_t*)dxln, mean, rstd, (const bf16_t*)hpre, ln_dw, ln_db, (long)M, 0, 0};
-    switch (C) {
-        case 96: return launch_mlp_bwd<96, true>(p, stream);
-        case 128: return launch_mlp_bwd<128, true>(p, stream);
-        case 192: return launch_mlp_bwd<192, true>(p, stream);
-        default: return launch_mlp_bwd<384, false>(p, stream);
+    CnArgs c = {};
+    c.M = M; c.C = C; c.operands = dy && xd && ln_w && ln_b && packed_bwd && b1 && dh && g && xln && dxln && mean && rstd;
+    c.hpre = hpre; c.ln_dw = ln_dw; c.ln_db = ln_db;
+    if (cn_check(CN_BWD, c)) return 1;
+    const CnPlan pl = cn_plan(CN_BWD, M, C, 0, ln_dw != nullptr, mmg_cu_count_cached(), cn_knobs());
+    const MlpBwd p{(const bf16_t*)dy, (const bf16_t*)xd, ln_w, ln_b, eps, (const bf16_t*)packed_bwd, b1, (bf16_t*)dh, (bf16_t*)g,
+                   (bf16_t*)xln, (bf16_t*)dxln, mean, rstd, (const bf16_t*)hpre, ln_dw, ln_db, (long)M, pl.ntiles, pl.nt};
+    MMG_NOTE_KERNEL("%s", cn_plan_name(pl));
+    switch (pl.kernel) {
+#define KB(C, RECOMP, LNB) case CK_bwd_##C##_##RECOMP##_##LNB: MLP_LAUNCH((cnblock_mlp_bwd_kernel<C, RECOMP, LNB>))
+        CN_BWD_KERNELS(KB)
+#undef KB
+        default: mmg_set_error("mmg_cnblock_mlp_bwd: no kernel for plan %d", pl.kernel); return 1;
     }
+    MMG_LAUNCH_CHECK("mmg_cnblock_mlp_bwd");
+    return 0;
 }

@@ -417,7 +417,8 @@ def dwconv7_wgrad(x, dy, dw49, dbias, n, H, W, C):
 
 
 def cnblock_supported(C):
-    return C in (96, 128, 192, 256, 384, 512)
+    """mmg_cnblock_mlp_fwd exists for this width: the library has a plan for it (csrc/cnblock_plan.hip; no launch, no device)."""
+    return bool(_hip.load().mmg_cnblock_plan(0, 64, int(C), 0, 0, 1))
 
 
 def cnblock_pack(w1, w2, gamma=None, backward=False):
@@ -482,8 +483,9 @@ def cnblock_mlp_bwd(dy, xd, ln_w, ln_b, eps, packed_bwd, b1, hpre=None, ln_grads
 
 
 def cnblock_bwdw_supported(C, M):
-    """On-chip weight-gradient backward of the CNBlock MLP (csrc/cnblock_bwdw.hip): C = 96, M a multiple of 64."""
-    return bool(_hip.load().mmg_cnblock_bwdw_supported(C)) and M % 64 == 0 and M * C * 2 < 2 ** 32
+    """On-chip weight-gradient backward of the CNBlock MLP (csrc/cnblock_bwdw.hip; C = 96, M a multiple of 64 below 4 GiB of rows):
+    mmg_cnblock_bwdw takes C at M rows, i.e. the library has a plan for them (no launch, no device)."""
+    return bool(_hip.load().mmg_cnblock_plan(2, int(M), int(C), 0, 0, 1))
 
 
 def cnblock_bwdw_pack(w1, w2, ln_w, ln_b, layer_scale, b1):

@@ -3,7 +3,8 @@ of csrc/cnblock_mlp.hip (mmg_cnblock_mlp_fwd, mmg_cnblock_mlp_bwd) and csrc/cnbl
 
 Imported by tests/test_cnblock_ref_cpu.py (no GPU: the table names every template instantiation, the exactness preconditions hold on
 the reference alone, the emulation is inside every bar and every mutation of it leaves them) and by tests/test_cnblock_gpu.py (the
-kernels against the same reference).  Everything here runs on the CPU in float64.
+kernels against the same reference); tests/test_cnblock_plan_cpu.py holds the library's plans (mmg_cnblock_plan) against the restatement
+of the launch rules below.  Everything here runs on the CPU in float64.
 
 The operation (x = xd [M, C], W1 [4C, C], W2 [C, 4C], ls = layer scale [C]; W1, W2 are given bf16-exact - the kernels' contract):
     mean, rstd = row statistics of x, rstd = (var + eps)^-1/2;  xhat = (x - mean) rstd;  xln = xhat ln_w + ln_b
@@ -171,6 +172,51 @@ def plan(case, cus):
     grid = min(cdiv(ntiles, rw), cus) if rw else min(ntiles, cap(case, cus))
     walkers = grid * (rw or 1)
     return dict(M=M, tile=tile, ntiles=ntiles, grid=grid, walkers=walkers, min_tiles=ntiles // walkers, max_tiles=cdiv(ntiles, walkers))
+
+
+def block(case):
+    """Threads per workgroup (cnblock_bwdw: of launch 1 and of launch 2)."""
+    if case.op == "bwdw":
+        return (768 if case.w12 else 512, 512)
+    rw = resident(case)
+    return 64 * (rw or (4 if case.C <= 256 else 8))
+
+
+def lds(case):
+    """Dynamic LDS bytes of the launch."""
+    C = case.C
+    if case.op == "bwdw":
+        # the W1 image and the dh image at a hidden pitch of 4C + 8, two row images at a pitch of 64 + 8 rows, ln_w, b1', the row statistics
+        return (C // 8) * (4 * C + 8) * 16 + 2 * (C // 8) * 72 * 16 + 4 * 4 * (4 * C + 8) * 8 + C * 4 + 4 * C * 4 + 2 * 64 * 2 * 4
+    NC = 64 if C <= 128 else 32
+    part = NC * C * 2                                   # one weight part of a chunk, bf16
+    if case.op == "bwd":
+        return 2 * ((3 if C != 384 else 2) * part) + 8 * C * 4
+    return (4 * C // NC if resident(case) else 2) * (2 * part) + 8 * C * 4
+
+
+def nt(case, M):
+    """Whether the 4C-wide outputs are stored past L2: the knob where it is set, else the backward from C = 128 at 256 MiB; a forward
+    that saves nothing has no such output."""
+    if case.op == "bwdw" or (case.op == "fwd" and not case.save):
+        return 0
+    if case.nt is not None:
+        return int(case.nt != 0)
+    return int(case.op == "bwd" and case.C >= 128 and M * 4 * case.C * 2 >= 256 << 20)
+
+
+def plan_text(case, cus):
+    """What mmg_cnblock_plan returns for the case on a device of `cus` CUs."""
+    pl = plan(case, cus)
+    b = block(case)
+    b = f"({b[0]},{b[1]})" if case.op == "bwdw" else str(b)
+    return f"{kernel_note(case)} grid={pl['grid']} block={b} lds={lds(case)} nt={nt(case, pl['M'])} tiles={pl['ntiles']}"
+
+
+def plan_args(case, cus):
+    """The arguments of mmg_cnblock_plan for the case."""
+    return ({"fwd": 0, "bwd": 1, "bwdw": 2}[case.op], rows(case, cus), case.C, int(bool(case.save)) if case.op == "fwd" else 0,
+            int(case.ln) if case.op == "bwd" else 0, cus)
 
 
 def instantiations(case):

@@ -7,7 +7,7 @@ Every case of cnblock_ref.CASES sets its knobs through the environment and runs 
 launches behind it) through mmgclip._hip.call on buffers of the test's own: every output is pre-filled with NaN bits and carries EXTRA
 sentinel rows past row M.  Integer cases: torch.equal against the reference cast to the output type for the outputs cnblock_ref lists
 as exact.  Everything else: the derived bars; every figure goes to `measured`.  Beside the numbers: the launch is the instantiation the
-table names (mmg_last_kernel), no output holds a NaN fill, every sentinel tail is intact, rows that are equal (the rows have period P)
+table names (mmg_last_kernel) and the one mmg_cnblock_plan names for this device, on the grid cnblock_ref.plan gives, no output holds a NaN fill, every sentinel tail is intact, rows that are equal (the rows have period P)
 give equal bits, and the tile-loop cases give every workgroup (wave) at least two tiles at this device's CU count.
 
 What these tests found: no wrong result.  On the parent's kernels every integer case was bit-exact and every gaussian figure inside
@@ -183,6 +183,9 @@ def test_kernels_against_float64(case, dev, monkeypatch):
                        + f" ({vals[k + '_differ']:.5f} of the elements differ from the reference cast to the output type)")
     if name != R.kernel_note(case):
         bad.append(f"launched {name!r}, the table says {R.kernel_note(case)!r}")
+    planned = _hip.load().mmg_cnblock_plan(*R.plan_args(case, cus)[:5], 0).decode()          # (the knobs are still the case's; cus = 0: this device)
+    if planned.split(" grid=")[0] != name or f" grid={pl['grid']} " not in planned:
+        bad.append(f"launched {name!r} on a grid of {pl['grid']}, mmg_cnblock_plan says {planned!r}")
     assert not bad, bad
 
 

@@ -24,8 +24,25 @@ def test_every_instantiation_is_launched_in_the_integer_regime():
     assert len({c.id for c in R.CASES}) == len(R.CASES)
 
 
-def test_kernel_notes_are_spelt_as_the_launchers_spell_them():
+def _library_note(monkeypatch, **kw):
+    """The same spelling from the library's own plan (mmg_cnblock_plan: no launch, no GPU), under the case's knobs."""
+    from mmgclip import _hip
+    case = R.Case(**{"regime": "integer", "M": 64, **kw})
+    for name, v in case.env.items():
+        if v is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, str(v))
+    return _hip.load().mmg_cnblock_plan(*R.plan_args(case, 256)).decode().split(" grid=")[0]
+
+
+def test_kernel_notes_are_spelt_as_the_launchers_spell_them(monkeypatch):
     note = lambda **kw: R.kernel_note(R.Case(**{"regime": "integer", "M": 64, **kw}))
+    _check_the_eight_spellings(note)
+    _check_the_eight_spellings(lambda **kw: _library_note(monkeypatch, **kw))
+
+
+def _check_the_eight_spellings(note):
     assert note(op="fwd", C=96) == "cnblock_mlp_fwd_kernel<96, false, 12>"
     assert note(op="fwd", C=96, res=8) == "cnblock_mlp_fwd_kernel<96, false, 8>"
     assert note(op="fwd", C=96, res=0) == "cnblock_mlp_fwd_kernel<96, false>"
