@@ -459,6 +459,27 @@ int mmg_sigmoid_rows_bwd(const float* X, const float* Y, const float* scale, con
 int mmg_retrieval_rows_rank(const float* X, const float* Y, const long long* row_key, const long long* col_label, int n_loc, int N,
                             int D, int diag_off, float* best, int* n_pos, int* n_gt, int* n_eq, mmg_stream_t stream);
 
+/* Nearest-neighbour search: the k best gallery columns of every local query, without an [n_loc,N] matrix (csrc/topk_head.hip; the
+ * reference has no search, its PromptClassifier scores a handful of prompts densely, mmgclip/networks/mmgclip_model.py:168-257).
+ * X [n_loc,D], Y [N,D] fp32; scores fp32 / indices int32 [n_loc,k] row-major; D % 32 == 0, 32 <= D <= 1024, 1 <= k <= 32.
+ *   s_ij = <X_i,Y_j> (no scale, no bias; the bits of mmg_retrieval_rows_rank's scores);  column j has the global index J = j_base + j
+ *   excluded: exclude 0 none (row_key, col_label NULL) | 1 J == diag_off + i (both NULL, diag_off >= 0; a diagonal outside this chunk
+ *             excludes nothing) | 2 col_label[j] == row_key[i] (int64 [N] / [n_loc], both given)
+ *   row i receives its k best admissible columns under the TOTAL order (score descending, then J ascending): scores as fp32, indices
+ *   as J; slots beyond the number of admissible columns hold -inf / -1 (k > N is legal).
+ *   accumulate != 0: the buffers hold a valid list (sorted by that order, padded with -inf / -1) from launches over OTHER columns;
+ *   the result is the top-k of the union.  accumulate == 0: every owned element is written, nothing beyond row n_loc is.
+ * The order is total, so the result is unique: bit-identical however the gallery is cut into launches, whichever rows share a launch
+ * and from run to run.  No atomics.  FINITE inputs are assumed; NaN is not defined.  j_base >= 0 and j_base + N fits int32.
+ * mmg_topk_rows_supported: 1 / 0, whether the staged rows (32 (D+4) 4 bytes) and the lists (4 x 32 x k x 8 bytes) fit the 160 KB of LDS:
+ * every D <= 992 with k <= 32, D = 1024 with k <= 31.  mmg_topk_rows_lds_bytes: the launch's dynamic LDS, 0 when unsupported.  Neither
+ * makes a HIP call; everything is validated before any HIP call.  Additive entry points: mmg_abi_version() stays 5. */
+int mmg_topk_rows_supported(int D, int k);
+int mmg_topk_rows_lds_bytes(int D, int k);
+int mmg_topk_rows(const float* X, const float* Y, int n_loc, int N, int D, int k, int exclude, const long long* row_key,
+                  const long long* col_label, int diag_off, int j_base, int accumulate, float* scores, int* indices,
+                  mmg_stream_t stream);
+
 /* Zero-shot AUROC with bootstrap replicates as exact integer pair counts (validation / evaluation; csrc/auroc_head.hip).
  *   U2[b] = sum_{i<P} sum_{j<Nn} w_pos[b][i] * w_neg[b][j] * g(s_pos[i], s_neg[j]),  g = 2 [s+ > s-] + [s+ == s-],
  *   AUROC_b = U2[b] / (2 * sum_i w_pos[b][i] * sum_j w_neg[b][j])   (the host divides; weights all 1 = the point estimate).

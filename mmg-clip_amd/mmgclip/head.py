@@ -1,6 +1,7 @@
 """Host side of the contrastive heads: autograd wrappers over the fp32 gfx950 kernels of csrc/clip_head.hip (CLIP),
 csrc/averaged_head.hip (AveragedMedicalCLIP) and csrc/sigmoid_head.hip (sigmoid pairwise), which share the tile skeleton of
-csrc/clip_tile.h, and the backend of the retrieval ranks at validation (csrc/retrieval_head.hip, same skeleton; mmgclip/retrieval.py).
+csrc/clip_tile.h, and the backend of the retrieval ranks at validation (csrc/retrieval_head.hip, same skeleton; mmgclip/retrieval.py)
+and of the nearest-neighbour search (csrc/topk_head.hip, same skeleton; mmgclip/search.py).
 
 Reference arithmetic (path:line in the reference tree):
     mmgclip/networks/mmgclip_model.py:128-136  normalise, exp(logit_scale), two logit matmuls
@@ -434,6 +435,37 @@ class _HipRetrievalBackend:
         call("mmg_retrieval_rows_rank", ptr(x_loc), ptr(y_all), ptr(row_key), ptr(col_label), n_loc, y_all.shape[0], D, diag_off,
              ptr(best), ptr(n_pos), ptr(n_gt), ptr(n_eq), stream())
         return best, n_pos, n_gt, n_eq
+
+
+class _HipTopKBackend:
+    """The product arithmetic of the nearest-neighbour search (mmgclip/search.py): the entry points of csrc/topk_head.hip.  As with
+    `_HipRetrievalBackend`, no product signature selects anything else; tests/test_topk_cpu.py replaces this module attribute in its
+    worker processes (gloo, CPU)."""
+
+    @staticmethod
+    def supported(D, k):
+        """Whether one launch can hold the staged rows and the candidate lists for this (D, k).  No GPU is needed."""
+        return bool(_hip.load().mmg_topk_rows_supported(int(D), int(k)))
+
+    @staticmethod
+    def topk(x_loc, y, k, exclude=0, row_key=None, col_label=None, diag_off=0, j_base=0, out=None):
+        """(scores fp32 [n,k], indices int32 [n,k]): the k best columns of `y` for every row of `x_loc` under (score descending, global
+        index j_base + j ascending), padded with -inf / -1.  exclude: 0 none, 1 the column diag_off + i, 2 col_label[j] == row_key[i].
+        `out` = (scores, indices) of earlier calls over OTHER columns: merged in place and returned.  No autograd, no [n,N] allocation."""
+        _hip.require_gpu(x_loc, y, row_key, col_label)
+        n_loc, D = x_loc.shape
+        if out is None:
+            scores = torch.empty((n_loc, k), device=x_loc.device, dtype=torch.float32)
+            indices = torch.empty((n_loc, k), device=x_loc.device, dtype=torch.int32)
+        else:
+            scores, indices = out
+            _hip.require_gpu(scores, indices)
+            if (scores.shape != (n_loc, k) or indices.shape != (n_loc, k) or scores.dtype != torch.float32 or indices.dtype != torch.int32
+                    or not (scores.is_contiguous() and indices.is_contiguous())):
+                raise ValueError("out must be contiguous (fp32 [n,k], int32 [n,k]) lists of earlier calls")
+        call("mmg_topk_rows", ptr(x_loc), ptr(y), n_loc, y.shape[0], D, k, exclude, ptr(row_key), ptr(col_label), diag_off, j_base,
+             0 if out is None else 1, ptr(scores), ptr(indices), stream())
+        return scores, indices
 
 
 class _HipAurocBackend:

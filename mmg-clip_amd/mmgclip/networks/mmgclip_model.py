@@ -319,3 +319,50 @@ class PromptClassifier(nn.Module):
             plt.title(f"{image_id}" + (f"  TP: {ground_truth}" if ground_truth else ""))
             plt.show()
         return outputs
+
+
+class ReportRetriever(PromptClassifier):
+    """Nearest-report search around an MMGCLIP model, beside `PromptClassifier` (additive: the reference has no search, only the
+    dense scoring of a handful of prompts above).  The tokenizer is resolved exactly as `PromptClassifier` resolves it, the hashed
+    stand-in included.
+
+    `build(texts)` encodes the strings once, in batches, into the normalised text embeddings the model's forward returns (the ones
+    `validate()` feeds to `RetrievalMetrics.update`) and keeps them in a `search.EmbeddingIndex`; `forward(image_features, k)` embeds
+    the images the same way and returns, per image, the k nearest strings under (score descending, index ascending):
+    `{"indices": int64 [n,k], "scores": fp32 [n,k], "texts": n lists of k strings}` (None where k exceeds the number of strings).
+    No [n,N] matrix is formed (csrc/topk_head.hip)."""
+
+    def __init__(self, model=None, tokenizer=None):
+        super().__init__(model=model, tokenizer=tokenizer)
+        self.texts = []
+        self.index = None
+
+    def _embed(self, features, projection):
+        if projection is not None:
+            features = projection(features)
+        return head.L2Normalize.apply(features).float().contiguous()
+
+    def build(self, texts, batch_size=256):
+        from ..search import EmbeddingIndex
+        texts = list(texts)
+        if not texts or any(not isinstance(t, str) for t in texts):
+            raise ValueError("build() needs a non-empty list of strings")
+        self.model.eval()
+        rows = []
+        with torch.no_grad():
+            for a in range(0, len(texts), batch_size):
+                feats = self.model.encode_text({"text_tokens": self._tokens(texts[a:a + batch_size])}, text_pooling='eos')
+                rows.append(self._embed(feats, self.model.text_projection_layer))
+        self.texts = texts
+        self.index = EmbeddingIndex(torch.cat(rows).contiguous())
+        return self
+
+    def forward(self, image_features, k=5):
+        if self.index is None:
+            raise RuntimeError("ReportRetriever.forward() before build(texts)")
+        self.model.eval()
+        with torch.no_grad():
+            queries = self._embed(self.model.encode_images({"image_features": image_features}), self.model.image_projection_layer)
+            scores, indices = self.index.search(queries, k)
+        return {"indices": indices, "scores": scores,
+                "texts": [[self.texts[j] if j >= 0 else None for j in row] for row in indices.tolist()]}
