@@ -480,6 +480,28 @@ int mmg_topk_rows(const float* X, const float* Y, int n_loc, int N, int D, int k
                   const long long* col_label, int diag_off, int j_base, int accumulate, float* scores, int* indices,
                   mmg_stream_t stream);
 
+/* Linear probe on frozen embeddings: the un-normalised loss, weight gradient and bias gradient of a multinomial logistic regression
+ * out of ONE read of X (csrc/probe_head.hip; the reference scores a shipped classifier head instead, mmgclip/evaluator.py
+ * evaluate_cnn / clf_conf_matrix).  X [n,D], W [C,D], b [C] fp32 contiguous (X, W 16-byte aligned); labels int64 [n]; class_weight
+ * fp32 [C] or NULL (weight 1); D % 32 == 0, 32 <= D <= 1024, 2 <= C <= 32, n >= 1.
+ *   z_ic = <X_i,W_c> + b_c;  w_i = class_weight[labels[i]];  a row whose label is outside [0,C) is ignored (the host admits -1 only)
+ *   L = sum_i w_i (logsumexp_c z_ic - z_{i,labels[i]});  dW[c][d] = sum_i w_i (p_ic - [c == labels[i]]) X[i][d];  db[c] likewise
+ *   out: fp64 [C (D+1) + 1] = dW | db as [C][D+1] row-major (column D is db), then L.  The host divides by sum_i w_i and adds L2.
+ * n_groups persistent workgroups (0 = one per CU; never more than ceil(n/32)), workgroup g takes the 32-row blocks g, g + n_groups, ..
+ * and writes partials[g] = { fp64 loss, fp32 [C][D+1] }, 8 + 4 C (D+1) bytes rounded up to 8; a second launch sums the partials in
+ * index order in fp64 into out.  partials and out 8-byte aligned; partials holds mmg_probe_rows_partials_bytes(n, D, C, n_groups)
+ * bytes (0 for arguments mmg_probe_rows rejects; n_groups <= 4096), every byte the second launch reads is written by the first.
+ * No atomics, one owner per element: bit-identical from run to run; a different n_groups regroups the fp32 sums.  p is e / sum by a
+ * true division (W = 0 with C a power of two gives exactly 1/C); padded classes and rows are selected to zero.  FINITE inputs.
+ * mmg_probe_rows_supported: 1 / 0 for (D, C), no HIP call.  mmg_probe_rows_partials_bytes with n_groups = 0 asks the CURRENT device
+ * for its CU count (HIP calls; 256 without a device), so it must be queried with the device current that will launch; with
+ * n_groups > 0 it makes no HIP call.  Everything is validated before any HIP call.  Additive entry points:
+ * mmg_abi_version() stays 5. */
+int mmg_probe_rows_supported(int D, int C);
+long long mmg_probe_rows_partials_bytes(int n, int D, int C, int n_groups);
+int mmg_probe_rows(const float* X, const float* W, const float* b, const long long* labels, const float* class_weight, int n, int D,
+                   int C, int n_groups, void* partials, double* out, mmg_stream_t stream);
+
 /* Zero-shot AUROC with bootstrap replicates as exact integer pair counts (validation / evaluation; csrc/auroc_head.hip).
  *   U2[b] = sum_{i<P} sum_{j<Nn} w_pos[b][i] * w_neg[b][j] * g(s_pos[i], s_neg[j]),  g = 2 [s+ > s-] + [s+ == s-],
  *   AUROC_b = U2[b] / (2 * sum_i w_pos[b][i] * sum_j w_neg[b][j])   (the host divides; weights all 1 = the point estimate).

@@ -1,5 +1,5 @@
-// The rows-against-Y tile skeleton of the contrastive heads (clip_head.hip, averaged_head.hip, sigmoid_head.hip; retrieval_head.hip
-// and topk_head.hip use stage_x / zt_tile): a workgroup owns 32
+// The rows-against-Y tile skeleton of the contrastive heads (clip_head.hip, averaged_head.hip, sigmoid_head.hip; retrieval_head.hip,
+// topk_head.hip and probe_head.hip use stage_x / zt_tile): a workgroup owns 32
 // local rows of X in LDS and streams 32-column tiles of Y, fp32 on v_mfma_f32_32x32x2_f32 issued "swapped" (A = Y tile, B = X tile)
 // so that a lane holds ONE row i and 16 columns j.  Written once here: the log-sum-exp forward (rows_lse_fwd_kernel), the backward
 // dX = s G Y with its two scalar gradients (rows_bwd_kernel) and their launchers.  A head supplies only a rule: where a row's label

@@ -11,6 +11,8 @@ labels from the batches), dispatches over `config.dataset.eval.enum_classes` x `
 under `config.base.results_export_dir`.  Not reproduced: the ROC / histogram PNG files (evaluator.py:386-460, plotting), the PrettyTable
 object of `zeroshot_eval` (a list of row dicts with the same columns instead) and `clf_conf_matrix` ("confustion_matrix": it scores the
 image classifier head of the ConvNeXt TorchScript archive, which the repo does not ship) - configured there, it is logged and skipped.
+Added: `linear_probe` (method value "linear_probe"), the supervised yardstick that needs no shipped classifier: a `probe.LinearProbe`
+fitted on the train loader's image embeddings and scored on the test loader's.
 """
 import numpy as np
 import torch
@@ -57,13 +59,15 @@ def label_prompts(key, classes_dict):
 
 
 class Evaluator:
-    def __init__(self, config, test_dataloader=None, tokenizer=None, model=None):
-        """`model`: a trained MMGCLIP instance; without one the checkpoint at config.checkpoints.* is loaded (evaluator.py:43-57)."""
+    def __init__(self, config, test_dataloader=None, tokenizer=None, model=None, train_dataloader=None):
+        """`model`: a trained MMGCLIP instance; without one the checkpoint at config.checkpoints.* is loaded (evaluator.py:43-57).
+        `train_dataloader`: the batches the "linear_probe" method fits on (optional; without it that method is logged and skipped)."""
         import os
         from .networks.mmgclip_model import MMGCLIP
         self.config = config
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.test_dataloader = test_dataloader
+        self.train_dataloader = train_dataloader
         self.tokenizer = tokenizer
         if model is not None:
             self.model = model
@@ -184,6 +188,75 @@ class Evaluator:
                          "F1": metrics.f1_score(y_true, y_pred)})
         return rows
 
+    def linear_probe_config(self):
+        """`config.dataset.eval.linear_probe` -> the keywords of `linear_probe`: a mapping with `l2` or `l2s` (a sweep), `max_iter`,
+        `class_weight`; absent = the probe's defaults."""
+        from .networks.mmgclip_model import _get
+        node = _get(self.config, "dataset.eval.linear_probe", None)
+        if node is None:
+            return {}
+        node = dict(node)
+        unknown = set(node) - {"l2", "l2s", "max_iter", "class_weight"}
+        if unknown:
+            raise ValueError(f"dataset.eval.linear_probe: unknown keys {sorted(unknown)}")
+        if "l2" in node and "l2s" in node:
+            raise ValueError("dataset.eval.linear_probe: give l2 or l2s, not both")
+        if "l2s" in node:
+            node["l2s"] = [float(v) for v in node["l2s"]]
+        return node
+
+    def linear_probe(self, train_embeddings, train_labels, test_embeddings, test_labels, classes_dict, key, ci="device", seed=0,
+                     n_iterations=1000, l2s=None, **probe_kw):
+        """The supervised yardstick: a `probe.LinearProbe` fitted on the train embeddings and scored on the test embeddings.  The
+        classes are `classes_dict` without `unknown` (as `clf_conf_matrix` leaves it out, evaluator.py:169-171), in its order; a train
+        row labelled `unknown` is ignored by the fit, a test row labelled `unknown` is left out of every figure.  Returns
+        {'accuracy', 'confusion_matrix' (nested list, row = true class, column = predicted), 'auc': {class: one-vs-rest AUROC},
+        ['auc_ci_mean', 'auc_ci_lower', 'auc_ci_higher' for two classes, of the second], 'l2', 'n_iter', 'converged'}.  The AUROC
+        figures come from `ZeroShotAUROC` on the class probabilities (`ci="device"`: with its seeded bootstrap; None: without).
+        `l2s`: sweep these strengths on every fifth train row held out (`LinearProbe.sweep` leaves the held-out rows labelled
+        `unknown` out of its AUROC), then refit on all rows with the best; `probe_kw` goes to `LinearProbe`.  A label name that is
+        neither a class nor `unknown` raises KeyError, as in `zeroshot_label_prompt`."""
+        from .probe import LinearProbe
+        from .zeroshot_auroc import ZeroShotAUROC
+        if ci not in ("device", None):
+            raise ValueError(f'ci must be "device" or None (the AUROC route is ZeroShotAUROC), got {ci!r}')
+        logger.info(f"Evaluating linear probe for {key}.")
+        names = [n for n in classes_dict if n != "unknown"]
+        index = {n: i for i, n in enumerate(names)}
+
+        index["unknown"] = -1                                # the one name that is left out; any other unexpected name is a KeyError
+
+        def targets(labels):
+            return torch.tensor([index[label[key].replace(' ', '').replace('-', '')] for label in labels], dtype=torch.int64)
+
+        def rows(e):
+            return torch.as_tensor(e, dtype=torch.float32, device=self.device).contiguous()
+        X_tr, y_tr = rows(train_embeddings), targets(train_labels).to(self.device)
+        y_te = targets(test_labels)
+        keep = torch.nonzero(y_te >= 0).flatten()
+        X_te, y_te = rows(test_embeddings)[keep.to(self.device)].contiguous(), y_te[keep]
+        C = len(names)
+        probe = LinearProbe(**probe_kw)
+        if l2s is not None:
+            held = torch.arange(X_tr.shape[0], device=self.device) % 5 == 4
+            probe.sweep(X_tr[~held].contiguous(), y_tr[~held].contiguous(), X_tr[held].contiguous(), y_tr[held].contiguous(), l2s,
+                        n_classes=C)
+        probe.fit(X_tr, y_tr, n_classes=C, warm_start=l2s is not None)
+        proba = probe.predict_proba(X_te)
+        y_pred = torch.argmax(proba, dim=1).cpu()
+        confusion = torch.zeros((C, C), dtype=torch.int64)
+        confusion.index_put_((y_te, y_pred), torch.ones_like(y_te), accumulate=True)
+        boot = C == 2 and ci == "device"
+        zs = ZeroShotAUROC(n_bootstrap=n_iterations if boot else 0, seed=seed)
+        zs.update(key, proba, y_te, list(range(C)))
+        classes = zs.compute()[key]["classes"]
+        results = {'accuracy': float((y_pred == y_te).double().mean()), 'confusion_matrix': confusion.tolist(),
+                   'auc': {name: classes[i]['auc'] for i, name in enumerate(names)}}
+        if boot:
+            results['auc_ci_mean'], results['auc_ci_lower'], results['auc_ci_higher'] = (classes[1][k] for k in ("ci_mean", "ci_lower", "ci_upper"))
+        results.update(l2=probe.l2, n_iter=probe.n_iter_, converged=probe.converged_)
+        return results
+
     @staticmethod
     def _named_labels(prompt_labels, key, classes_dict):
         """The reference's datasets hand label NAMES over (`label[key]` is an enum member's name, evaluator.py:326); synthetic
@@ -205,6 +278,7 @@ class Evaluator:
         methods = list(self.config.dataset.eval.method)
         out_dir = create_directory_if_not_exists(self.config.base.results_export_dir)
         experiments_results = []
+        train = None                                         # (labels, embeddings) of the train loader, encoded once when a probe asks
         for enum_class_name in self.config.dataset.eval.enum_classes:
             if enum_class_name not in ENUMS:
                 raise ValueError(f"Invalid enum class: {enum_class_name}")
@@ -227,6 +301,24 @@ class Evaluator:
             if "confustion_matrix" in methods:       # (sic: the reference's spelling of the config value)
                 logger.warning("`confustion_matrix` scores the image classifier of the ConvNeXt TorchScript archive, which is not part "
                                "of this build: skipped")
+            if "linear_probe" in methods:
+                if self.train_dataloader is None:
+                    logger.warning("`linear_probe` fits on train embeddings and no train dataloader was given: skipped")
+                    continue
+                if train is None:
+                    train = ([], [])
+                    with torch.no_grad():
+                        for batch in self.train_dataloader:
+                            train[0].extend(batch['prompt_labels'])
+                            train[1].append(self.encode_image(batch, as_numpy=False))
+                    train = (train[0], torch.cat(train[1], 0))
+                if any(enum_class_name not in label for label in train[0]):
+                    logger.warning(f"train batches carry no `{enum_class_name}` labels: linear probe skipped")
+                    continue
+                results = self.linear_probe(train[1], self._named_labels(train[0], enum_class_name, classes_dict), image_embeddings, labels,
+                                            classes_dict, enum_class_name, **self.linear_probe_config())
+                logger.info(f"Results From linear probe evaluation...\n{results}\n")
+                experiments_results.append(results)
         with open(os.path.join(out_dir, 'results.txt'), 'w') as file:
             for result in experiments_results:
                 file.write(str(result) + '\n\n')

@@ -1,7 +1,8 @@
 """Host side of the contrastive heads: autograd wrappers over the fp32 gfx950 kernels of csrc/clip_head.hip (CLIP),
 csrc/averaged_head.hip (AveragedMedicalCLIP) and csrc/sigmoid_head.hip (sigmoid pairwise), which share the tile skeleton of
 csrc/clip_tile.h, and the backend of the retrieval ranks at validation (csrc/retrieval_head.hip, same skeleton; mmgclip/retrieval.py)
-and of the nearest-neighbour search (csrc/topk_head.hip, same skeleton; mmgclip/search.py).
+and of the nearest-neighbour search (csrc/topk_head.hip, same skeleton; mmgclip/search.py) and of the linear probe
+(csrc/probe_head.hip, same skeleton; mmgclip/probe.py).
 
 Reference arithmetic (path:line in the reference tree):
     mmgclip/networks/mmgclip_model.py:128-136  normalise, exp(logit_scale), two logit matmuls
@@ -466,6 +467,35 @@ class _HipTopKBackend:
         call("mmg_topk_rows", ptr(x_loc), ptr(y), n_loc, y.shape[0], D, k, exclude, ptr(row_key), ptr(col_label), diag_off, j_base,
              0 if out is None else 1, ptr(scores), ptr(indices), stream())
         return scores, indices
+
+
+class _HipProbeBackend:
+    """The product arithmetic of the linear probe (mmgclip/probe.py): the entry points of csrc/probe_head.hip.  As with
+    `_HipTopKBackend`, no product signature selects anything else; tests/test_probe_cpu.py replaces this module attribute in its
+    worker processes (gloo, CPU)."""
+
+    @staticmethod
+    def supported(D, C):
+        """Whether the fused kernel takes this (D, C): D a multiple of 32 in [32,1024], 2 <= C <= 32.  No GPU is needed."""
+        return bool(_hip.load().mmg_probe_rows_supported(int(D), int(C)))
+
+    @staticmethod
+    def evaluate(x, W, b, labels, class_weight=None, n_groups=0):
+        """fp64 [C (D+1) + 1] on the device: the un-normalised dW | db as [C, D+1] (column D is db), then the loss L, of the rows
+        `x` [n,D] with int64 `labels` (-1 = ignored) at the fp32 weights W [C,D], b [C]; `class_weight` fp32 [C] or None.  One read
+        of `x`, no [n,C] temporary, no atomics: the same bits from run to run.  n_groups: the persistent grid, 0 = one per CU."""
+        _hip.require_gpu(x, W, b, labels, class_weight)
+        n, D = x.shape
+        C = W.shape[0]
+        nbytes = _hip.load().mmg_probe_rows_partials_bytes(n, D, C, int(n_groups))
+        if nbytes <= 0:
+            raise ValueError(f"the probe kernel takes D % 32 == 0 in [32,1024], 2 <= C <= 32, n >= 1 and 0 <= n_groups <= 4096; "
+                             f"got n={n} D={D} C={C} n_groups={n_groups}")
+        partials = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+        out = torch.empty(C * (D + 1) + 1, device=x.device, dtype=torch.float64)
+        call("mmg_probe_rows", ptr(x), ptr(W), ptr(b), ptr(labels), ptr(class_weight), n, D, C, int(n_groups), ptr(partials), ptr(out),
+             stream())
+        return out
 
 
 class _HipAurocBackend:
