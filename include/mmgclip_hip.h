@@ -689,6 +689,30 @@ int mmg_vit_assemble_bwd(const void* g, void* dtok, float* dpos, float* dcls, in
  * its backward is mmg_eos_pool_bwd. */
 int mmg_gather_rows_fwd(const void* hidden, const int* idx, float* out, int B, int S, int H, mmg_stream_t stream);
 
+/* ---- patch dropout for the ViT tower (csrc/patch_dropout.hip) ---------------------------------------------------
+ * FLIP (Li et al. 2023) / open_clip's `patch_dropout`: under train() an image keeps K of its P patches plus the class token and the
+ * encoder runs on 1 + K tokens.  No reference counterpart (its image encoders are ConvNeXt-T / ResNet-50, mmgclip/networks/encoder.py:15,57).
+ * Every argument is validated before any HIP call; no atomics, one writer per element: bit-reproducible.  K in 1 .. P everywhere.
+ * Additive entry points: mmg_abi_version() stays 5.
+ * mmg_patch_keep_indices: the draw of csrc/dropout.h under site 0x50447270,
+ *     bits_p = mmg_drop_bits(p, mmg_drop_key_bh(mmg_drop_key(seed, site), (unsigned) sample_ids[b])),   sample_ids NULL: sample id b;
+ *   image b keeps the K patches with the smallest bits_p (a bijection of p: no ties).  keep int32 [B,K]: their indices, ascending;
+ *   slot int32 [B,P]: the position of patch p among the kept ones of image b, or -1.  sample_ids: device int64 [B] or NULL.
+ *   One workgroup per image, the keys in LDS: P <= 16384. */
+int mmg_patch_keep_indices(unsigned long long seed, const long long* sample_ids, int B, int P, int K, int* keep, int* slot,
+                           mmg_stream_t stream);
+/* out bf16 [B*K,Kp] = the rows b*P + keep[b,j] of p0 bf16 [B*P, Kp] (row stride ld elements); Kp % 8 == 0, ld % 8 == 0, 16-byte aligned. */
+int mmg_gather_patch_rows(const void* p0, long long ld, const int* keep, void* out, int B, int P, int K, int Kp, mmg_stream_t stream);
+/* mmg_vit_assemble_fwd on the kept tokens, positions as before the drop: out bf16 [B, 1+K, H];
+ * out[b,0,:] = cls + pos[0]; out[b,1+j,:] = tok[b*K+j,:] + pos[1+keep[b,j],:]; pos is the full table [1+P, H].  H % 8 == 0. */
+int mmg_vit_assemble_keep_fwd(const void* tok, const void* cls, const void* pos, const int* keep, void* out, int B, int P, int K,
+                              int H, mmg_stream_t stream);
+/* g bf16 [B, 1+K, H] -> dtok bf16 [B*K, H] = g rows 1..; dpos fp32 [1+P, H]: dpos[1+p] += the sum, in ascending b, of g[b, 1+slot[b,p]] over
+ * the images that kept p (a row that nobody kept is not touched); dpos[0] and dcls[H] += sum_b g[b,0,:]: the bits of mmg_vit_assemble_bwd
+ * on the full gradient that is zero at the dropped rows. */
+int mmg_vit_assemble_keep_bwd(const void* g, const int* slot, void* dtok, float* dpos, float* dcls, int B, int P, int K, int H,
+                              mmg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,9 +117,10 @@ class ViTB16Encoder(ViTTower):
     """ViT-B/16 on raw pixels (BASELINE config C4; torchvision `vit_b_16` state-dict layout, class-token pooling)."""
 
     def __init__(self, pretrained=None, image_features_dimension=None, in_chans=1, scale16=True, micro_batch=256, freeze=False,
-                 image_size=224, layers=12, checkpoint=False, augment=None):
+                 image_size=224, layers=12, checkpoint=False, augment=None, patch_dropout=0.0):
+        # patch_dropout: networks.image_encoder.patch_dropout - the fraction of patches a training-mode forward drops (mmgclip/patch_dropout.py)
         super().__init__(image_size=image_size, in_chans=in_chans, layers=layers, scale16=scale16, micro_batch=micro_batch,
-                         checkpoint=checkpoint, augment=augment)
+                         checkpoint=checkpoint, augment=augment, patch_dropout=patch_dropout)
         if isinstance(pretrained, str) and os.path.isfile(pretrained):
             sd = _load_state_file(pretrained)
             self.model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("heads.")}, strict=True)

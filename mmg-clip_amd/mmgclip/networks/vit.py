@@ -9,6 +9,10 @@ ln_2, mlp.{0,3}}`, `encoder.ln`; LayerNorm eps 1e-6, erf-GELU, no dropout.  The 
 All layers reuse the BERT/ConvNeXt kernels: the 16x16/16 patch convolution is `mmg_patchify` + GEMM, attention is
 `mmg_attention_fwd/bwd` without a key mask (whole sequence in LDS) up to S = 256 tokens (224x224 -> 197) and the
 flash-style tiled `mmg_attention_long_fwd/bwd` beyond (1024x1024 -> S = 4097, BASELINE config C4).
+
+`patch_dropout` (FLIP / open_clip; mmgclip/patch_dropout.py, csrc/patch_dropout.hip): under train() every image keeps K of its patches and
+the class token, drawn once per forward on the device; the kept rows are gathered before the patch-embedding GEMM and every layer runs at
+S = 1 + K.  eval() and rate 0 take the code path above unchanged.
 """
 import torch
 import torch.nn as nn
@@ -16,6 +20,7 @@ import torch.nn as nn
 from .. import _hip
 from .. import kernels as K
 from .. import linalg as L
+from .. import patch_dropout as PD
 from .._hip import call, ptr, stream
 from ..params import backward_finished
 from .tower import Tower, as_pixels, augment_tables, backward_parts, conv_weight_rows, fold_conv_grad, forward_parts
@@ -57,9 +62,14 @@ class ViTTower(Tower):
     """pixels [n, Cin, H, W], fp32 in [0,1] or raw uint16 / uint8 -> class-token features [n, hidden].  augment: as ConvNextTower's."""
 
     def __init__(self, image_size=224, in_chans=1, hidden=768, layers=12, heads=12, mlp_dim=3072, patch=16, scale16=True,
-                 micro_batch=256, checkpoint=False, augment=None):
+                 micro_batch=256, checkpoint=False, augment=None, patch_dropout=0.0):
         super().__init__()
         self.set_augment(augment)
+        # FLIP's patch dropout (mmgclip/patch_dropout.py): under train() every image keeps K of its patches and the class token, and every
+        # layer runs on 1 + K tokens; eval() sees every patch.  May be reassigned between steps (FLIP's unmasked tuning at the end of a run).
+        self.patch_dropout = patch_dropout
+        self.next_patch_drop_seed = None    # tests: force the seed of the next forward that drops patches
+        self._patch_drop_seeds = PD.PatchDropSeeds()
         self.checkpoint = checkpoint        # keep only each micro-batch's pixels, re-run its forward inside its backward
         assert hidden == 64 * heads, "the attention kernel is specialised for head_dim 64"
         self.image_size, self.in_chans, self.hidden, self.layers, self.heads = image_size, in_chans, hidden, layers, heads
@@ -68,6 +78,41 @@ class ViTTower(Tower):
         self.model = _tv_layout(image_size, in_chans, hidden, layers, mlp_dim, patch)
         self.model_output_dimension = hidden
         self.kp = (patch * patch * in_chans + 31) // 32 * 32
+
+    @property
+    def patch_dropout(self):
+        return self._patch_dropout
+
+    @patch_dropout.setter
+    def patch_dropout(self, rate):
+        self._patch_dropout = PD.check_rate(rate)
+
+    def patch_dropout_active(self):
+        return self.training and self._patch_dropout > 0.0
+
+    def _draw_patch_drop(self, count, sample_ids, device):
+        """One draw per forward: -> (keep int32 [count, K], slot int32 [count, P]) on `device`, made in one launch for the whole input, or None
+        when no patch is dropped (eval(), or rate 0: no seed is drawn and nothing is launched).  sample_ids: as Tower._draw_augment's."""
+        if not self.patch_dropout_active():
+            return None
+        if self.next_patch_drop_seed is not None:
+            seed, self.next_patch_drop_seed = int(self.next_patch_drop_seed), None
+        else:
+            seed = self._patch_drop_seeds.draw()
+        P = self.seq - 1
+        Kk = PD.keep_count(P, self._patch_dropout)
+        if P > PD.MAX_PATCHES:
+            raise ValueError(f"patch_dropout draws an image's {P} patches in one workgroup, which holds {PD.MAX_PATCHES}")
+        ids = None
+        if sample_ids is not None:
+            ids = [int(i) for i in sample_ids]
+            if len(ids) != count:
+                raise ValueError(f"sample_ids names {len(ids)} images, the input holds {count}")
+            ids = torch.tensor(ids, dtype=torch.int64).to(device)
+        keep = torch.empty(count, Kk, device=device, dtype=torch.int32)
+        slot = torch.empty(count, P, device=device, dtype=torch.int32)
+        call("mmg_patch_keep_indices", seed & 0xFFFFFFFFFFFFFFFF, ptr(ids), count, P, Kk, ptr(keep), ptr(slot), stream())
+        return keep, slot
 
     def _blk(self, i):
         return getattr(self.model.encoder.layers, f"encoder_layer_{i}")
@@ -84,14 +129,25 @@ class ViTTower(Tower):
                 wc[f"{i}.{tag}t"] = K.transpose_cast_bf16(wt)
         return wc
 
-    def _forward_mb(self, img, save, tabs=None):
-        wc, H, S, heads = self._wc, self.hidden, self.seq, self.heads
-        B = img.shape[0]
+    def _forward_mb(self, img, save, tabs=None, drop=None):
+        """drop: None, or this micro-batch's (keep [B, K], slot [B, P]) rows of _draw_patch_drop: the kept rows of the patchified pixels are
+        gathered BEFORE the patch-embedding GEMM, and every layer runs at S = 1 + K."""
+        wc, H, heads = self._wc, self.hidden, self.heads
+        B, P = img.shape[0], self.seq - 1
         p0 = K.patchify(img, self.patch, self.kp, self.scale16, *(tabs or (None, None)))
+        if drop is not None:
+            keep, Kk = drop[0], drop[0].shape[1]
+            kept = torch.empty(B * Kk, self.kp, device=img.device, dtype=torch.bfloat16)
+            call("mmg_gather_patch_rows", ptr(p0), self.kp, ptr(keep), ptr(kept), B, P, Kk, self.kp, stream())
+            p0 = kept
+        S = self.seq if drop is None else 1 + Kk
         tok = L.gemm_nt(p0, wc["conv"], bias=self.model.conv_proj.bias.data)
         x = torch.empty(B * S, H, device=img.device, dtype=torch.bfloat16)
-        call("mmg_vit_assemble_fwd", ptr(tok), ptr(wc["cls"]), ptr(wc["pos"]), ptr(x), B, S, H, stream())
-        saved = {"p0": p0, "layers": [], "B": B} if save else None
+        if drop is None:
+            call("mmg_vit_assemble_fwd", ptr(tok), ptr(wc["cls"]), ptr(wc["pos"]), ptr(x), B, S, H, stream())
+        else:
+            call("mmg_vit_assemble_keep_fwd", ptr(tok), ptr(wc["cls"]), ptr(wc["pos"]), ptr(keep), ptr(x), B, P, Kk, H, stream())
+        saved = {"p0": p0, "layers": [], "B": B, "S": S, "drop": drop} if save else None
         del tok
         for i in range(self.layers):
             b = self._blk(i)
@@ -117,8 +173,8 @@ class ViTTower(Tower):
         return feat, saved
 
     def _backward_mb(self, dfeat, saved):
-        wc, A, H, S, heads = self._wc, self._arena, self.hidden, self.seq, self.heads
-        B = saved["B"]
+        wc, A, H, heads = self._wc, self._arena, self.hidden, self.heads
+        B, S, drop = saved["B"], saved["S"], saved["drop"]
         x, mf, rf, idx = saved["final"]
         ln = self.model.encoder.ln
         dout = K.eos_pool_bwd(dfeat, idx, B, S)
@@ -155,14 +211,18 @@ class ViTTower(Tower):
             del dy, dx1
             saved["layers"][i] = None
         dtok = torch.empty(B * (S - 1), H, device=dx.device, dtype=torch.bfloat16)
-        call("mmg_vit_assemble_bwd", ptr(dx), ptr(dtok), ptr(A.g("encoder.pos_embedding")), ptr(A.g("class_token")), B, S, H, stream())
+        if drop is None:
+            call("mmg_vit_assemble_bwd", ptr(dx), ptr(dtok), ptr(A.g("encoder.pos_embedding")), ptr(A.g("class_token")), B, S, H, stream())
+        else:
+            call("mmg_vit_assemble_keep_bwd", ptr(dx), ptr(drop[1]), ptr(dtok), ptr(A.g("encoder.pos_embedding")), ptr(A.g("class_token")),
+                 B, self.seq - 1, S - 1, H, stream())
         tmp = torch.zeros(H, self.kp, device=dx.device, dtype=torch.float32)
         L.gemm_tn_acc(dtok, saved["p0"], tmp, colsum=A.g("conv_proj.bias"))
         fold_conv_grad(tmp, A.g("conv_proj.weight"), H, self.in_chans, self.patch, self.patch)
 
     def forward(self, images, sample_ids=None):
         """images: [n, Cin, S, S] (fp32 in [0,1], or raw uint16 / uint8), or a list of [Cin, S, S] images, S = image_size.
-        sample_ids (augmentation): the number under which image i draws, default i - its position in this input."""
+        sample_ids (augmentation, patch dropout): the number under which image i draws, default i - its position in this input."""
         if isinstance(images, (list, tuple)):
             if not images or any(not torch.is_tensor(t) or t.dim() != 3 for t in images):
                 raise ValueError("a list of images must hold [Cin, H, W] tensors")
@@ -174,21 +234,24 @@ class ViTTower(Tower):
         if images.shape[-1] != self.image_size or images.shape[-2] != self.image_size:
             raise ValueError(f"ViT was built for {self.image_size}x{self.image_size} inputs (learned positions), got {tuple(images.shape)}")
         anchor = self._record_forward(images.device)
-        return _ViTFn.apply(self, as_pixels(images).contiguous(), anchor, self._draw_augment(images.shape[0], sample_ids))
+        return _ViTFn.apply(self, as_pixels(images).contiguous(), anchor, self._draw_augment(images.shape[0], sample_ids),
+                            self._draw_patch_drop(images.shape[0], sample_ids, images.device))
 
 
 class _ViTFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tower, images, anchor, aug=None):
+    def forward(ctx, tower, images, anchor, aug=None, drop=None):
         """aug: None, or the (geom rows, tone rows) of a forward that augments (Tower._draw_augment): uploaded once, a slice per micro-batch,
-        kept with the part so that a checkpointed recomputation reads the same rows."""
+        kept with the part so that a checkpointed recomputation reads the same rows.  drop: None, or the (keep, slot) tables of a forward
+        that drops patches (ViTTower._draw_patch_drop): made once on the device, sliced and kept with the part the same way."""
         tower._refresh_working_copies()
         save = anchor is not None
         mb, count = tower.micro_batch, images.shape[0]
         starts = range(0, count, mb)
         tabs = augment_tables(aug, [list(range(i, min(i + mb, count))) for i in starts], images.device) if aug is not None else [None] * len(starts)
-        parts = [(lambda i=i, tab=tab: (images[i:i + mb], tab)) for i, tab in zip(starts, tabs)]
-        out, parts = forward_parts(parts, lambda x, saving: tower._forward_mb(x[0], save and saving, x[1]), save and tower.checkpoint)
+        drops = [(drop[0][i:i + mb], drop[1][i:i + mb]) if drop is not None else None for i in starts]
+        parts = [(lambda i=i, tab=tab, dr=dr: (images[i:i + mb], tab, dr)) for i, tab, dr in zip(starts, tabs, drops)]
+        out, parts = forward_parts(parts, lambda x, saving: tower._forward_mb(x[0], save and saving, x[1], x[2]), save and tower.checkpoint)
         ctx.tower, ctx.parts = tower, parts if save else None
         return out
 
@@ -197,6 +260,6 @@ class _ViTFn(torch.autograd.Function):
         tower = ctx.tower
         tower._arena.prepare_grads()
         dfeat = dfeat.float().contiguous()
-        backward_parts(ctx.parts, dfeat, lambda x: tower._forward_mb(x[0], True, x[1])[1], lambda d, saved, last: tower._backward_mb(d, saved))
+        backward_parts(ctx.parts, dfeat, lambda x: tower._forward_mb(x[0], True, x[1], x[2])[1], lambda d, saved, last: tower._backward_mb(d, saved))
         backward_finished(tower)
-        return None, None, None, None
+        return None, None, None, None, None
