@@ -701,6 +701,23 @@ int mmg_gather_rows_fwd(const void* hidden, const int* idx, float* out, int B, i
  *   One workgroup per image, the keys in LDS: P <= 16384. */
 int mmg_patch_keep_indices(unsigned long long seed, const long long* sample_ids, int B, int P, int K, int* keep, int* slot,
                            mmg_stream_t stream);
+/* The foreground prior: the same draw made aware of the image, in two launches (additive: mmg_abi_version() stays 5).
+ * mmg_patch_foreground: counts int32 [n, (H/patch)*(W/patch)], counts[i,p] = the foreground elements among the Cin*patch*patch canvas
+ *   elements of patch p, under mmg_patchify_aug's geometry to the letter: src_kind 0 = fp32, 1 = uint16, 2 = uint8; geom (device, nullable =
+ *   identity) int32 [n,4] = flags, ty, tx, 0; the same inside test, flips over the full H, W and fill; remainder rows / columns beyond
+ *   floor(H/patch)*patch, floor(W/patch)*patch ignored.  A canvas element is foreground iff inside && x01 > threshold, x01 = r |
+ *   float(r)/65535 | float(r)/255 in fp32 (IEEE division), BEFORE any tone: what is tissue does not depend on the brightness jitter.  A fill
+ *   pixel and a NaN are background.  threshold in [0, 1).  Every pixel is read once, coalesced along x for any W and row alignment; integer
+ *   counts, no global atomics, one writer per output.
+ * mmg_patch_keep_indices_prior: patch p of image b is foreground iff counts[b,p] >= min_pixels (>= 1), and the image keeps the K patches
+ *   smallest under (0 if foreground else 1, bits_p), bits_p as in mmg_patch_keep_indices: every foreground patch before any background
+ *   patch, the hash inside each class.  nfg >= K: a hash-uniform K-subset of the foreground; nfg < K: all of it plus the K - nfg background
+ *   patches of smallest bits; a row of one class (nfg 0 or NP) equals mmg_patch_keep_indices' row bit for bit.  keep, slot: as there;
+ *   n_foreground (nullable) int32 [B] = nfg.  One workgroup per image, keys and class flags in LDS: NP <= 16384. */
+int mmg_patch_foreground(const void* img, int src_kind, int n, int Cin, int H, int W, int patch, const int* geom, float threshold,
+                         int* counts, mmg_stream_t stream);
+int mmg_patch_keep_indices_prior(unsigned long long seed, const long long* sample_ids, const int* counts, int min_pixels, int B, int NP,
+                                 int K, int* keep, int* slot, int* n_foreground, mmg_stream_t stream);
 /* out bf16 [B*K,Kp] = the rows b*P + keep[b,j] of p0 bf16 [B*P, Kp] (row stride ld elements); Kp % 8 == 0, ld % 8 == 0, 16-byte aligned. */
 int mmg_gather_patch_rows(const void* p0, long long ld, const int* keep, void* out, int B, int P, int K, int Kp, mmg_stream_t stream);
 /* mmg_vit_assemble_fwd on the kept tokens, positions as before the drop: out bf16 [B, 1+K, H];

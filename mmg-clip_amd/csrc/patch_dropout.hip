@@ -10,7 +10,11 @@
 // and the image keeps the K patches with the smallest bits_p, in ascending patch order.  mmg_drop_bits is fmix32 of an odd multiple of p
 // plus a constant, a bijection of the 32-bit p: two patches of an image never draw the same bits, so "the K smallest" needs no tie rule.
 //
-// Four memory-bound kernels, no atomics, every output element written by exactly one thread: bit-reproducible.  The row movers read and
+// Under the foreground prior (mmg_patch_keep_indices_prior) a class bit goes in front of that key: a patch is foreground iff
+// counts[b, p] >= min_pixels, where counts comes from mmg_patch_foreground (the pixels above a threshold per patch, under patchify's
+// geometry), and the image keeps the K smallest (0 if foreground else 1, bits_p): tissue before background, the hash inside each class.
+//
+// Memory-bound kernels, no global atomics, every output element written by exactly one thread: bit-reproducible.  The row movers read and
 // write 16 bytes per lane, as vit_assemble_kernel (csrc/embedding.hip), and index with 64-bit offsets.
 #include "common.h"
 #include "dropout.h"
@@ -30,9 +34,16 @@ __device__ __forceinline__ void unpack8p(const uint4 v, float* f) {
 //      patch p is kept iff rank_p < K;
 //   3. an exclusive prefix count of the kept flags over the workgroup (wave scan + 16 wave totals) gives slot[b, p];
 //   4. keep[b, slot] = p: ascending by construction.
-template <int CH>
+// PRIOR: the key is (class, bits), class 0 = foreground (counts[b, p] >= min_pixels).  The class flags sit in LDS behind the keys, one bit
+// per patch (a wave's ballot is two words; the padding is background), and step 2 counts inside the patch's own class only:
+//     rank_p = #{q of p's class : bits_q < bits_p} + (p is background ? n_foreground : 0).
+// The flag of q is the same for every lane, so the key that q is compared against - mine for the lanes whose patch has q's class, 0 (below
+// which nothing is) for the others - is one select per compare.  A row of one class gets the ranks, and so the bits, of the plain draw.
+template <int CH, bool PRIOR>
 __global__ __launch_bounds__(PD_THREADS) void patch_keep_kernel(unsigned key0, const long long* __restrict__ sample_ids,
-                                                                int* __restrict__ keep, int* __restrict__ slot, int P, int K) {
+                                                                const int* __restrict__ counts, int min_pixels,
+                                                                int* __restrict__ keep, int* __restrict__ slot,
+                                                                int* __restrict__ n_foreground, int P, int K) {
     extern __shared__ unsigned pd_keys[];
     __shared__ int wave_tot[PD_THREADS / 64];
     const int b = blockIdx.x, t = threadIdx.x;
@@ -40,6 +51,18 @@ __global__ __launch_bounds__(PD_THREADS) void patch_keep_kernel(unsigned key0, c
     const unsigned key = mmg_drop_key_bh(key0, id);
     const int P4 = (P + 3) & ~3;
     for (int p = t; p < P4; p += PD_THREADS) pd_keys[p] = p < P ? mmg_drop_bits((unsigned)p, key) : 0xFFFFFFFFu;
+    unsigned* pd_flags = pd_keys + P4;                  // PRIOR: 2 * ceil(P / 64) words, bit (p & 31) of word p >> 5
+    if (PRIOR) {
+        for (int base = 0; base < P; base += PD_THREADS) {         // (every lane of a wave takes every trip: the ballot needs them all)
+            const int p = base + t;
+            const bool fg = p < P && counts[(size_t)b * P + p] >= min_pixels;
+            const unsigned long long m = __ballot(fg);
+            if ((t & 63) == 0 && p < P) {
+                pd_flags[p >> 5] = (unsigned)m;
+                pd_flags[(p >> 5) + 1] = (unsigned)(m >> 32);
+            }
+        }
+    }
     __syncthreads();
     unsigned mine[CH];
     int rank[CH];
@@ -49,13 +72,40 @@ __global__ __launch_bounds__(PD_THREADS) void patch_keep_kernel(unsigned key0, c
         mine[c] = p < P ? pd_keys[p] : 0u;          // (rank 0 for a patch that does not exist; masked below)
         rank[c] = 0;
     }
-    if (t * CH < P) {
-        for (int q = 0; q < P4; q += 4) {
+    if (!PRIOR) {
+        if (t * CH < P) {
+            for (int q = 0; q < P4; q += 4) {
+                const uint4 k4 = *reinterpret_cast<const uint4*>(pd_keys + q);
+#pragma unroll
+                for (int c = 0; c < CH; ++c)
+                    rank[c] += (int)(k4.x < mine[c]) + (int)(k4.y < mine[c]) + (int)(k4.z < mine[c]) + (int)(k4.w < mine[c]);
+            }
+        }
+    } else if (t * CH < P) {
+        unsigned as_fg[CH], as_bg[CH];              // what a foreground / a background q is compared against
+        bool bg[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int p = t * CH + c;
+            const bool fg = p < P && ((pd_flags[p >> 5] >> (p & 31)) & 1u);
+            bg[c] = p < P && !fg;
+            as_fg[c] = fg ? mine[c] : 0u;
+            as_bg[c] = bg[c] ? mine[c] : 0u;
+        }
+        int nfg = 0;
+        for (int q = 0; q < P4; q += 4) {           // (q % 4 == 0: the four flags of a step lie in one word)
             const uint4 k4 = *reinterpret_cast<const uint4*>(pd_keys + q);
+            const unsigned f4 = (pd_flags[q >> 5] >> (q & 31)) & 15u;
+            nfg += __popc(f4);
 #pragma unroll
             for (int c = 0; c < CH; ++c)
-                rank[c] += (int)(k4.x < mine[c]) + (int)(k4.y < mine[c]) + (int)(k4.z < mine[c]) + (int)(k4.w < mine[c]);
+                rank[c] += (int)(k4.x < ((f4 & 1u) ? as_fg[c] : as_bg[c])) + (int)(k4.y < ((f4 & 2u) ? as_fg[c] : as_bg[c])) +
+                           (int)(k4.z < ((f4 & 4u) ? as_fg[c] : as_bg[c])) + (int)(k4.w < ((f4 & 8u) ? as_fg[c] : as_bg[c]));
         }
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+            if (bg[c]) rank[c] += nfg;
+        if (t == 0 && n_foreground) n_foreground[b] = nfg;
     }
     unsigned flags = 0;
 #pragma unroll
@@ -88,22 +138,162 @@ __global__ __launch_bounds__(PD_THREADS) void patch_keep_kernel(unsigned key0, c
     }
 }
 
+template <bool PRIOR>
+static void patch_keep_launch(unsigned long long seed, const long long* sample_ids, const int* counts, int min_pixels, int B, int P, int K,
+                              int* keep, int* slot, int* n_foreground, hipStream_t stream) {
+    const unsigned key0 = mmg_drop_key(seed, PD_SITE);
+    const size_t lds = ((size_t)((P + 3) & ~3) + (PRIOR ? 2 * (size_t)cdiv(P, 64) : 0)) * sizeof(unsigned);
+    if (P <= PD_THREADS)
+        hipLaunchKernelGGL((patch_keep_kernel<1, PRIOR>), dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, counts, min_pixels, keep,
+                           slot, n_foreground, P, K);
+    else if (P <= 4 * PD_THREADS)
+        hipLaunchKernelGGL((patch_keep_kernel<4, PRIOR>), dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, counts, min_pixels, keep,
+                           slot, n_foreground, P, K);
+    else {
+        mmg_allow_lds(patch_keep_kernel<16, PRIOR>, lds);      // P = 16384: 64 KiB of keys (and 2 KiB of flags) beside the wave totals
+        hipLaunchKernelGGL((patch_keep_kernel<16, PRIOR>), dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, counts, min_pixels,
+                           keep, slot, n_foreground, P, K);
+    }
+}
+
 MMG_API int mmg_patch_keep_indices(unsigned long long seed, const long long* sample_ids, int B, int P, int K, int* keep, int* slot,
                                    hipStream_t stream) {
     MMG_CHECK_ARG(keep && slot && B > 0 && P > 0, "mmg_patch_keep_indices: bad argument");
     MMG_CHECK_ARG(P <= PD_MAX_P, "mmg_patch_keep_indices: P=%d patches per image, the workgroup's LDS layout holds %d", P, PD_MAX_P);
     MMG_CHECK_ARG(K >= 1 && K <= P, "mmg_patch_keep_indices: K=%d must be in 1 .. P=%d", K, P);
-    const unsigned key0 = mmg_drop_key(seed, PD_SITE);
-    const size_t lds = (size_t)((P + 3) & ~3) * sizeof(unsigned);
-    if (P <= PD_THREADS)
-        hipLaunchKernelGGL(patch_keep_kernel<1>, dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, keep, slot, P, K);
-    else if (P <= 4 * PD_THREADS)
-        hipLaunchKernelGGL(patch_keep_kernel<4>, dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, keep, slot, P, K);
-    else {
-        mmg_allow_lds(patch_keep_kernel<16>, lds);      // P = 16384: 64 KiB of keys beside the wave totals
-        hipLaunchKernelGGL(patch_keep_kernel<16>, dim3(B), dim3(PD_THREADS), lds, stream, key0, sample_ids, keep, slot, P, K);
-    }
+    patch_keep_launch<false>(seed, sample_ids, nullptr, 0, B, P, K, keep, slot, nullptr, stream);
     MMG_LAUNCH_CHECK("mmg_patch_keep_indices");
+    return 0;
+}
+
+MMG_API int mmg_patch_keep_indices_prior(unsigned long long seed, const long long* sample_ids, const int* counts, int min_pixels, int B,
+                                         int NP, int K, int* keep, int* slot, int* n_foreground, hipStream_t stream) {
+    MMG_CHECK_ARG(counts && keep && slot && B > 0 && NP > 0, "mmg_patch_keep_indices_prior: bad argument");
+    MMG_CHECK_ARG(NP <= PD_MAX_P, "mmg_patch_keep_indices_prior: NP=%d patches per image, the workgroup's LDS layout holds %d", NP, PD_MAX_P);
+    MMG_CHECK_ARG(K >= 1 && K <= NP, "mmg_patch_keep_indices_prior: K=%d must be in 1 .. NP=%d", K, NP);
+    MMG_CHECK_ARG(min_pixels >= 1, "mmg_patch_keep_indices_prior: min_pixels=%d must be at least 1 (0 would call every patch foreground)",
+                  min_pixels);
+    patch_keep_launch<true>(seed, sample_ids, counts, min_pixels, B, NP, K, keep, slot, n_foreground, stream);
+    MMG_LAUNCH_CHECK("mmg_patch_keep_indices_prior");
+    return 0;
+}
+
+// counts[i, ho * Wo + wo] = the foreground elements among the Cin * P * P canvas elements of patch (ho, wo) of image i, under the geometry of
+// mmg_patchify_aug (csrc/pixel_input.hip) to the letter: canvas pixel (y, x) reads ys = y - ty, xs = x - tx, inside = 0 <= ys < H &&
+// 0 <= xs < W, then the flips over the full H, W; it is foreground iff inside && x01 > threshold, x01 = r | float(r) / 65535 | float(r) / 255
+// before any tone.  A fill pixel and a NaN are background.  For the integer kinds x01 is a non-decreasing function of r, so
+// "float(r) / div > threshold" holds exactly for r >= rmin, the smallest such r: the host finds it by bisection WITH that division
+// (fg_rmin), and the kernel compares integers - the same predicate for every r at no division per pixel.
+//
+// One workgroup per (image, row of patches).  It walks the SOURCE rows that land on its Cin * P canvas rows in 16-byte chunks aligned in
+// memory (4 / 8 / 16 pixels), consecutive lanes on consecutive chunks, so a row of any W and any alignment is read coalesced: a chunk that
+// lies wholly inside its row is one wide load, a chunk across a row's end guarded scalar loads.  Only the source columns [s_lo, s_hi) that
+// land on canvas columns 0 .. Wo*P - 1 count.  A lane follows its chunk's canvas column (ascending, or descending under a flip over x) and
+// adds its count to the LDS counter of a patch column whenever it leaves one: integer adds in LDS, then one writer per output.
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void patch_foreground_kernel(const T* __restrict__ img, int Cin, int H, int W, int P,
+                                                               const int* __restrict__ geom, float threshold, unsigned rmin,
+                                                               int* __restrict__ counts) {
+    extern __shared__ int fg_cnt[];                     // [Wo]
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const int Ho = H / P, Wo = W / P, Wc = Wo * P, t = threadIdx.x;
+    const int ho = (int)(blockIdx.x % (unsigned)Ho);
+    const size_t n = blockIdx.x / (unsigned)Ho;
+    for (int i = t; i < Wo; i += 256) fg_cnt[i] = 0;
+    __syncthreads();
+    int flags = 0;
+    long long ty = 0, tx = 0;
+    if (geom) {
+        const int4 g = reinterpret_cast<const int4*>(geom)[n];
+        flags = g.x; ty = g.y; tx = g.z;
+    }
+    const bool flipx = flags & 1, flipy = flags & 2;
+    // canvas column of source column s: x = s + tx, or tx + W-1-s under the flip; the source columns with 0 <= x < Wc
+    long long s_lo = flipx ? tx + W - Wc : -tx, s_hi = flipx ? tx + W : (long long)Wc - tx;
+    if (s_lo < 0) s_lo = 0;
+    if (s_hi > W) s_hi = W;
+    if (s_lo < s_hi) {
+        const int nch = (int)((s_hi - s_lo + VEC - 1) / VEC) + 1;       // chunks a row's [s_lo, s_hi) can touch, whatever its alignment
+        const int items = Cin * P * nch;
+        for (int item = t; item < items; item += 256) {
+            const int r = item / nch, jj = item - r * nch;
+            const int ci = r / P, kh = r - ci * P;
+            long long ys = (long long)ho * P + kh - ty;
+            if (ys < 0 || ys >= H) continue;
+            if (flipy) ys = H - 1 - ys;
+            const T* line = img + ((n * Cin + ci) * H + (size_t)ys) * W;
+            const int mis = (int)((reinterpret_cast<uintptr_t>(line) / sizeof(T)) & (VEC - 1));    // pixels past a 16-byte boundary
+            // chunk j holds the source columns j * VEC - mis .. + VEC - 1
+            const long long c0 = ((s_lo + mis) / VEC + jj) * VEC - mis;
+            if (c0 >= s_hi) continue;
+            T v[VEC];
+            if (c0 >= 0 && c0 + VEC <= W) {
+                const uint4 u = *reinterpret_cast<const uint4*>(line + c0);
+                __builtin_memcpy(v, &u, 16);
+            } else {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) v[e] = (c0 + e >= 0 && c0 + e < W) ? line[c0 + e] : (T)0;
+            }
+            // the chunk touches [s_lo, s_hi), so its first canvas column lies within VEC of 0 .. Wc - 1
+            const int x0 = (int)(flipx ? tx + W - 1 - c0 : c0 + tx);
+            int q = x0 >= 0 ? x0 / P : -((P - 1 - x0) / P);             // floor(x0 / P)
+            int rem = x0 - q * P, cnt = 0;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const bool fg = KIND == 0 ? (float)v[e] > threshold : (unsigned)v[e] >= rmin;
+                if (c0 + e >= s_lo && c0 + e < s_hi && fg) ++cnt;
+                rem += flipx ? -1 : 1;
+                if (rem < 0 || rem >= P) {                              // the next pixel belongs to another patch column
+                    if (cnt) atomicAdd(&fg_cnt[q], cnt);
+                    cnt = 0;
+                    q += flipx ? -1 : 1;
+                    rem = flipx ? P - 1 : 0;
+                }
+            }
+            if (cnt) atomicAdd(&fg_cnt[q], cnt);
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < Wo; i += 256) counts[((size_t)n * Ho + ho) * Wo + i] = fg_cnt[i];
+}
+
+// smallest r in 0 .. maxv with float(r) / div > threshold, maxv + 1 if there is none (the quotient does not decrease with r)
+static unsigned fg_rmin(float threshold, float div, unsigned maxv) {
+    unsigned lo = 0, hi = maxv + 1;
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) / 2;
+        if ((float)mid / div > threshold) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+MMG_API int mmg_patch_foreground(const void* img, int src_kind, int n, int Cin, int H, int W, int patch, const int* geom, float threshold,
+                                 int* counts, hipStream_t stream) {
+    MMG_CHECK_ARG(img && counts, "mmg_patch_foreground: null %s", img ? "counts" : "img");
+    MMG_CHECK_ARG(src_kind >= 0 && src_kind <= 2, "mmg_patch_foreground: unknown src_kind %d (0 = fp32, 1 = uint16, 2 = uint8)", src_kind);
+    MMG_CHECK_ARG(n > 0 && Cin > 0 && patch > 0 && H >= patch && W >= patch,
+                  "mmg_patch_foreground: bad argument (n=%d Cin=%d H=%d W=%d patch=%d)", n, Cin, H, W, patch);
+    MMG_CHECK_ARG(threshold >= 0.0f && threshold < 1.0f, "mmg_patch_foreground: threshold=%g must be in [0, 1)", (double)threshold);
+    // (what the kernel indexes with an int: a patch's count, a workgroup's (row, chunk) items, the grid; and its LDS counters)
+    MMG_CHECK_ARG((long long)Cin * patch * patch <= 0x7fffffffLL && (long long)Cin * patch * (W / 4 + 2) <= 0x7fffffffLL &&
+                  (long long)n * (H / patch) <= 0x7fffffffLL && W / patch <= 16384,
+                  "mmg_patch_foreground: Cin * patch * max(patch, W / 4 + 2) and n * (H / patch) must fit 31 bits, W / patch <= 16384");
+    MMG_CHECK_ARG((reinterpret_cast<uintptr_t>(geom) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(img) & (src_kind == 0 ? 3 : (src_kind == 1 ? 1 : 0))) == 0,
+                  "mmg_patch_foreground: misaligned pointer (geom rows are 16 bytes, pixels their own width)");
+    const dim3 grid((unsigned)((long long)n * (H / patch)));
+    const size_t lds = (size_t)(W / patch) * sizeof(int);
+    if (src_kind == 0)
+        hipLaunchKernelGGL((patch_foreground_kernel<float, 0>), grid, dim3(256), lds, stream, (const float*)img, Cin, H, W, patch, geom,
+                           threshold, 0u, counts);
+    else if (src_kind == 1)
+        hipLaunchKernelGGL((patch_foreground_kernel<unsigned short, 1>), grid, dim3(256), lds, stream, (const unsigned short*)img, Cin, H, W,
+                           patch, geom, threshold, fg_rmin(threshold, 65535.0f, 65535u), counts);
+    else
+        hipLaunchKernelGGL((patch_foreground_kernel<unsigned char, 2>), grid, dim3(256), lds, stream, (const unsigned char*)img, Cin, H, W,
+                           patch, geom, threshold, fg_rmin(threshold, 255.0f, 255u), counts);
+    MMG_LAUNCH_CHECK("mmg_patch_foreground");
     return 0;
 }
 

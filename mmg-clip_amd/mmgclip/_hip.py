@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("MMGCLIP_HIP_LIB", os.path.join(_PKG_ROOT, "csrc", "li
 HEADER_PATH = os.path.join(_REPO_ROOT, "include", "mmgclip_hip.h")
 ABI_VERSION = 5      # 5: mmg_dwconv7_nhwc_mfma (round 4); 2: mmg_cnblock_mlp_fwd gained the optional xln output; the dropout entry points; 3: kernel-name notes; 4: cnblock_mlp_fwd gact, NT epilogue 5
                      # (mmg_view_pool_fwd / mmg_view_pool_bwd, then mmg_image_swap / mmg_image_copy / mmg_scaled_add_f32 were added at 5:
-                     #  purely additive symbols, no existing prototype changed; so were the four patch-dropout entry points)
+                     #  purely additive symbols, no existing prototype changed; so were the four patch-dropout entry points and the foreground prior's two)
 
 _CTYPES = {
     "int": ctypes.c_int,

@@ -117,10 +117,14 @@ class ViTB16Encoder(ViTTower):
     """ViT-B/16 on raw pixels (BASELINE config C4; torchvision `vit_b_16` state-dict layout, class-token pooling)."""
 
     def __init__(self, pretrained=None, image_features_dimension=None, in_chans=1, scale16=True, micro_batch=256, freeze=False,
-                 image_size=224, layers=12, checkpoint=False, augment=None, patch_dropout=0.0):
+                 image_size=224, layers=12, checkpoint=False, augment=None, patch_dropout=0.0, patch_prior="uniform", patch_threshold=0.0,
+                 patch_min_pixels=1, patch_dropout_eval=False):
         # patch_dropout: networks.image_encoder.patch_dropout - the fraction of patches a training-mode forward drops (mmgclip/patch_dropout.py)
+        # patch_prior, patch_threshold, patch_min_pixels, patch_dropout_eval: networks.image_encoder.* - which patches it keeps ("foreground":
+        # tissue first) and whether eval() keeps K patches as well
         super().__init__(image_size=image_size, in_chans=in_chans, layers=layers, scale16=scale16, micro_batch=micro_batch,
-                         checkpoint=checkpoint, augment=augment, patch_dropout=patch_dropout)
+                         checkpoint=checkpoint, augment=augment, patch_dropout=patch_dropout, patch_prior=patch_prior,
+                         patch_threshold=patch_threshold, patch_min_pixels=patch_min_pixels, patch_dropout_eval=patch_dropout_eval)
         if isinstance(pretrained, str) and os.path.isfile(pretrained):
             sd = _load_state_file(pretrained)
             self.model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("heads.")}, strict=True)

@@ -59,7 +59,10 @@ class MMGCLIP(nn.Module):
                 in_chans=_get(ie, "in_chans", 1), scale16=_get(ie, "scale16", True), micro_batch=_get(ie, "micro_batch", 64),
                 freeze=_get(ie, "freeze", False),
                 checkpoint=_get(ie, "checkpoint", False), augment=_get(ie, "augment"),
-                **({"image_size": _get(ie, "image_size", 224), "patch_dropout": _get(ie, "patch_dropout", 0.0)} if enc_name == "ViTB16Encoder" else
+                **({"image_size": _get(ie, "image_size", 224), "patch_dropout": _get(ie, "patch_dropout", 0.0),
+                    "patch_prior": _get(ie, "patch_prior", "uniform"), "patch_threshold": _get(ie, "patch_threshold", 0.0),
+                    "patch_min_pixels": _get(ie, "patch_min_pixels", 1), "patch_dropout_eval": _get(ie, "patch_dropout_eval", False)}
+                   if enc_name == "ViTB16Encoder" else
                    {"fp8": _get(ie, "fp8", False), "stochastic_depth_prob": _get(ie, "stochastic_depth_prob", 0.0)})).to(self.device)
             logger.info(f"Using {self.image_encoder.__class__.__name__}")
 

@@ -12,7 +12,10 @@ flash-style tiled `mmg_attention_long_fwd/bwd` beyond (1024x1024 -> S = 4097, BA
 
 `patch_dropout` (FLIP / open_clip; mmgclip/patch_dropout.py, csrc/patch_dropout.hip): under train() every image keeps K of its patches and
 the class token, drawn once per forward on the device; the kept rows are gathered before the patch-embedding GEMM and every layer runs at
-S = 1 + K.  eval() and rate 0 take the code path above unchanged.
+S = 1 + K.  eval() and rate 0 take the code path above unchanged.  `patch_prior="foreground"` makes that draw foreground first
+(`mmg_patch_foreground` counts the pixels above `patch_threshold` per patch under the forward's own augmentation geometry,
+`mmg_patch_keep_indices_prior` puts the patches with at least `patch_min_pixels` of them in front), and `patch_dropout_eval` keeps the same K
+under eval() from the pixels alone.  The default prior, "uniform", launches nothing new.
 """
 import torch
 import torch.nn as nn
@@ -62,12 +65,19 @@ class ViTTower(Tower):
     """pixels [n, Cin, H, W], fp32 in [0,1] or raw uint16 / uint8 -> class-token features [n, hidden].  augment: as ConvNextTower's."""
 
     def __init__(self, image_size=224, in_chans=1, hidden=768, layers=12, heads=12, mlp_dim=3072, patch=16, scale16=True,
-                 micro_batch=256, checkpoint=False, augment=None, patch_dropout=0.0):
+                 micro_batch=256, checkpoint=False, augment=None, patch_dropout=0.0, patch_prior="uniform", patch_threshold=0.0,
+                 patch_min_pixels=1, patch_dropout_eval=False):
         super().__init__()
+        self._patch_elements = in_chans * patch * patch     # the most a patch can count (patch_min_pixels' range)
         self.set_augment(augment)
         # FLIP's patch dropout (mmgclip/patch_dropout.py): under train() every image keeps K of its patches and the class token, and every
         # layer runs on 1 + K tokens; eval() sees every patch.  May be reassigned between steps (FLIP's unmasked tuning at the end of a run).
         self.patch_dropout = patch_dropout
+        # The foreground prior (mmgclip/patch_dropout.py): the same K, tissue first.  All four may be reassigned between steps, too.
+        self._patch_dropout_eval = False
+        self.patch_prior, self.patch_threshold, self.patch_min_pixels = patch_prior, patch_threshold, patch_min_pixels
+        self.patch_dropout_eval = patch_dropout_eval        # under eval() keep K patches as well, drawn from the pixels alone
+        self.last_patch_foreground = None   # (n_foreground int32 [n] on the device, K) of the last forward that drew under the prior
         self.next_patch_drop_seed = None    # tests: force the seed of the next forward that drops patches
         self._patch_drop_seeds = PD.PatchDropSeeds()
         self.checkpoint = checkpoint        # keep only each micro-batch's pixels, re-run its forward inside its backward
@@ -87,15 +97,57 @@ class ViTTower(Tower):
     def patch_dropout(self, rate):
         self._patch_dropout = PD.check_rate(rate)
 
+    @property
+    def patch_prior(self):
+        return self._patch_prior
+
+    @patch_prior.setter
+    def patch_prior(self, prior):
+        PD.check_dropout_eval(self._patch_dropout_eval, PD.check_prior(prior))
+        self._patch_prior = prior
+
+    @property
+    def patch_threshold(self):
+        return self._patch_threshold
+
+    @patch_threshold.setter
+    def patch_threshold(self, threshold):
+        self._patch_threshold = PD.check_threshold(threshold)
+
+    @property
+    def patch_min_pixels(self):
+        return self._patch_min_pixels
+
+    @patch_min_pixels.setter
+    def patch_min_pixels(self, min_pixels):
+        self._patch_min_pixels = PD.check_min_pixels(min_pixels, self._patch_elements)
+
+    @property
+    def patch_dropout_eval(self):
+        return self._patch_dropout_eval
+
+    @patch_dropout_eval.setter
+    def patch_dropout_eval(self, flag):
+        self._patch_dropout_eval = PD.check_dropout_eval(flag, self._patch_prior)
+
     def patch_dropout_active(self):
-        return self.training and self._patch_dropout > 0.0
+        return self._patch_dropout > 0.0 and (self.training or self._patch_dropout_eval)
 
     def _draw_patch_drop(self, count, sample_ids, device):
         """One draw per forward: -> (keep int32 [count, K], slot int32 [count, P]) on `device`, made in one launch for the whole input, or None
         when no patch is dropped (eval(), or rate 0: no seed is drawn and nothing is launched).  sample_ids: as Tower._draw_augment's."""
         if not self.patch_dropout_active():
             return None
-        if self.next_patch_drop_seed is not None:
+        seed, ids, P, Kk, keep, slot = self._patch_drop_arguments(count, sample_ids, device)
+        call("mmg_patch_keep_indices", seed & 0xFFFFFFFFFFFFFFFF, ptr(ids), count, P, Kk, ptr(keep), ptr(slot), stream())
+        return keep, slot
+
+    def _patch_drop_arguments(self, count, sample_ids, device, seed=None):
+        """What both draws take: the forward's seed (`seed` if given; else the forced one, else the next of the tower's stream), the sample
+        ids on the device (or None), P, K and the empty tables."""
+        if seed is not None:
+            pass
+        elif self.next_patch_drop_seed is not None:
             seed, self.next_patch_drop_seed = int(self.next_patch_drop_seed), None
         else:
             seed = self._patch_drop_seeds.draw()
@@ -111,7 +163,31 @@ class ViTTower(Tower):
             ids = torch.tensor(ids, dtype=torch.int64).to(device)
         keep = torch.empty(count, Kk, device=device, dtype=torch.int32)
         slot = torch.empty(count, P, device=device, dtype=torch.int32)
-        call("mmg_patch_keep_indices", seed & 0xFFFFFFFFFFFFFFFF, ptr(ids), count, P, Kk, ptr(keep), ptr(slot), stream())
+        return seed, ids, P, Kk, keep, slot
+
+    def _draw_patch_drop_prior(self, pixels, sample_ids, aug):
+        """The foreground-first draw, once per forward for the whole input: -> (keep, slot) as _draw_patch_drop's, and
+        self.last_patch_foreground = (n_foreground int32 [n] on the device, K).  pixels: the input as the stem will read it ([n, Cin, H, W],
+        contiguous); aug: Tower._draw_augment's rows of this forward or None - the counts are taken under the geometry rows patchify will use
+        for the same image.  A row is a pure function of (seed, sample id, the image's pixels, its geometry row): the same under any
+        micro_batch, and the tables stay with their part for a checkpointed recomputation.
+        Under eval() (patch_dropout_eval) every image draws under seed 0 and sample id 0 with no geometry, and the training stream is not
+        touched: the kept set, and so the embedding, is a function of the image's pixels alone."""
+        n, Cin, Hh, Ww = pixels.shape
+        device = pixels.device
+        if self.training:
+            seed, ids, P, Kk, keep, slot = self._patch_drop_arguments(n, sample_ids, device)
+            geom = torch.tensor(aug[0], dtype=torch.int32).reshape(-1, 4).to(device) if aug is not None else None
+        else:
+            seed, ids, P, Kk, keep, slot = self._patch_drop_arguments(n, [0] * n, device, seed=0)
+            geom = None
+        counts = torch.empty(n, P, device=device, dtype=torch.int32)
+        nfg = torch.empty(n, device=device, dtype=torch.int32)
+        call("mmg_patch_foreground", ptr(pixels), K.PIXEL_KINDS[pixels.dtype], n, Cin, Hh, Ww, self.patch, ptr(geom), self._patch_threshold,
+             ptr(counts), stream())
+        call("mmg_patch_keep_indices_prior", seed & 0xFFFFFFFFFFFFFFFF, ptr(ids), ptr(counts), self._patch_min_pixels, n, P, Kk, ptr(keep),
+             ptr(slot), ptr(nfg), stream())
+        self.last_patch_foreground = (nfg, Kk)
         return keep, slot
 
     def _blk(self, i):
@@ -234,8 +310,14 @@ class ViTTower(Tower):
         if images.shape[-1] != self.image_size or images.shape[-2] != self.image_size:
             raise ValueError(f"ViT was built for {self.image_size}x{self.image_size} inputs (learned positions), got {tuple(images.shape)}")
         anchor = self._record_forward(images.device)
-        return _ViTFn.apply(self, as_pixels(images).contiguous(), anchor, self._draw_augment(images.shape[0], sample_ids),
-                            self._draw_patch_drop(images.shape[0], sample_ids, images.device))
+        pixels = as_pixels(images).contiguous()
+        aug = self._draw_augment(images.shape[0], sample_ids)
+        self.last_patch_foreground = None
+        if self._patch_prior == "foreground" and self.patch_dropout_active():
+            drop = self._draw_patch_drop_prior(pixels, sample_ids, aug)
+        else:
+            drop = self._draw_patch_drop(images.shape[0], sample_ids, images.device)
+        return _ViTFn.apply(self, pixels, anchor, aug, drop)
 
 
 class _ViTFn(torch.autograd.Function):
