@@ -290,6 +290,18 @@ int mmg_dwconv7_nhwc_mfma(const void* x, const float* w, const float* bias, cons
 /* dw[49][C] += sum x(shifted) * dy ; dbias[C] += sum dy  (fp32, accumulated; dbias nullable) */
 int mmg_dwconv7_wgrad(const void* x, const void* dy, float* dw, float* dbias, int n, int H, int W, int C,
                       mmg_stream_t stream);
+/* What a depthwise 7x7 entry point WOULD launch, without launching: the plan its host layer makes (csrc/dwconv_plan.h; the three entry points
+ * validate, make one plan and launch the kernel it names) as text - the exact mmg_last_kernel() spelling, then
+ * " grid=(x,y,z) block=T lds=B nt=0|1 tile=HxW items=N" (B = dynamic LDS bytes, nt = the output is stored past L2: 256 MiB and more, never the
+ * weight gradient; tile = pixels per tile; N = n x tiles, the (image, tile) pairs of one 32-channel slab) and, for op 1, " add=0|1 by_image=0|1"
+ * (the ADD instantiation, which the kernel's name does not spell; by_image: n >= 8, an image's tiles stay with one XCD group).
+ * op: 0 mmg_dwconv7_nhwc, 1 mmg_dwconv7_nhwc_mfma, 2 mmg_dwconv7_wgrad; flip, add (ops 0, 1): as the entry point's flip, and whether its add
+ * operand is given; cus (read by op 1 only): CU count the plan is made for, 0 = the current device's.  MMG_DWCONV_ROWS2 / MMG_DWCONV_TH /
+ * MMG_DWG_TH / MMG_DWG_ALIGN / MMG_DWM_WAVES are honoured as by a launch.  A shape the entry point would reject gives "" and sets
+ * mmg_last_error() to that entry point's message.  The string belongs to the calling thread and is valid until its next call; no GPU is
+ * needed unless op == 1 and cus == 0.  No reference counterpart (diagnostics; tests/test_dwconv_plan_cpu.py pins kernel selection and launch
+ * geometry with it).  Additive entry point: mmg_abi_version() stays 5. */
+const char* mmg_dwconv7_plan(int op, int n, int H, int W, int C, int flip, int add, int cus);
 
 /* ---- fused ConvNeXt block MLP (C in {96,128,192,256,384,512}) ---------------------------------------------------------- */
 

@@ -10,16 +10,7 @@
 // slides the 7-tap window over a row of 14 inputs held in registers (56 packed FMAs per 14 LDS reads).
 // The same kernel with the taps flipped is the data gradient; the weight gradient keeps the 49 taps of its channel
 // pair in registers across tiles and images and reduces through LDS into one atomic per tap per workgroup.
-#include "common.h"
-#include <stdlib.h>
-
-#define DW_TW 32
-#define DW_TH 8
-#define DW_CB 32
-#define DW_COLS (DW_TW + 6)
-#define DW_ROWS (DW_TH + 6)
-#define DW_ROWD (DW_COLS * (DW_CB / 2) + 16)   // dwords per LDS row; +16 keeps rows r, r+1 on disjoint bank halves
-// DW_TH = 8 keeps the tile at 34 KiB so four workgroups share a CU (latency hiding for the LDS-read / FMA phases)
+#include "dwconv_plan.h"     // DW_TW / DW_TH / DW_CB / DW_COLS / DW_ROWS / DW_ROWD / DW_ROWD2: the tile, shared with the host's LDS arithmetic
 
 // Addressing.  The kernels are bound by VALU ISSUE (profiles/r02_dwconv_pmc.txt: 53 % of their VALU instructions were not FMAs), and
 // 64-bit pixel addresses cost quarter-rate v_mul_lo_u32 / v_mad_u64_u32 chains per load and store.  So: the image base
@@ -155,8 +146,6 @@ __global__ __launch_bounds__(256, 2) void dwconv7_kernel(const bf16_t* __restric
 // 224 unpacks + 1568 FMAs per lane instead of 392 + 1568, in one pass.  Every output accumulates its 49 taps in the same
 // (kh, kw) order as above: bit-identical results.  The row pitch is 616 dwords so that the four row groups of a wave, now
 // two rows apart, still start 16 banks apart.
-#define DW_ROWD2 (DW_COLS * (DW_CB / 2) + 8)
-#define DW_FWD_TH_DEFAULT 8
 // TH = tile height: 8 (four workgroups per CU) or 16 (two passes over one staged 22-row tile, two workgroups per CU: halo 1.21x
 // instead of 1.4x, staging and tap loads amortised over twice the pixels).
 template <bool FLIP, int TH>
@@ -440,55 +429,29 @@ __global__ __launch_bounds__(256, 1) void dwconv7_wgrad_rows2_kernel(const bf16_
     }
 }
 
-static int dw_check(const char* who, int n, int H, int W, int C) {
-    MMG_CHECK_ARG(n > 0 && H > 0 && W > 0 && C > 0 && C % DW_CB == 0 && n <= 65535 && C / DW_CB <= 65535,
-                  "%s: n=%d H=%d W=%d C=%d (C must be a multiple of 32)", who, n, H, W, C);
-    // 32-bit byte offsets inside one image, 24-bit pixel indices (dw_byte_off)
-    MMG_CHECK_ARG((long long)(H + 16) * (W + 64) <= (1LL << 24) && (long long)H * W * C * 2 < (1LL << 32),
-                  "%s: one image of %d x %d x %d exceeds the kernels' 32-bit addressing (H * W <= 2^24, H * W * C * 2 < 2^32)", who, H, W, C);
-    return 0;
-}
+// ---- the doors: validate (dwconv_plan.hip, before any HIP call), plan, launch what the plan names ---------------------------------------------
+#define DW_LAUNCH(KERNEL, ...)                                                                                              \
+    mmg_allow_lds(KERNEL, pl.lds);                                                                                          \
+    hipLaunchKernelGGL((KERNEL), dim3(pl.gx, pl.gy, pl.gz), dim3(pl.block), pl.lds, stream, __VA_ARGS__);                   \
+    break;
 
 // y = dwconv7(x; w, bias) (+ add).  w is tap-major fp32 [49][C] (w[kh*7+kw][c] = weight[c,0,kh,kw]).
 // flip != 0 uses the taps reversed: with x := dy this is the gradient w.r.t. the input.
 MMG_API int mmg_dwconv7_nhwc(const void* x, const float* w, const float* bias, const void* add, void* y, int n, int H,
                              int W, int C, int flip, hipStream_t stream) {
-    MMG_CHECK_ARG(x && w && y, "mmg_dwconv7_nhwc: null pointer");
-    if (dw_check("mmg_dwconv7_nhwc", n, H, W, C)) return 1;
-    const int tiles_w = cdiv(W, DW_TW), tiles_h = cdiv(H, DW_TH);
-    const size_t shm = (size_t)DW_ROWS * DW_ROWD * 4 + 49 * DW_CB * 4;
-    const dim3 grid(tiles_w * tiles_h, C / DW_CB, n);
-    const int nt = (size_t)n * H * W * C * 2 >= ((size_t)256 << 20);
-    const int rows2 = getenv("MMG_DWCONV_ROWS2") ? atoi(getenv("MMG_DWCONV_ROWS2")) : 1;      // read per call (tests / A-B runs)
-    if (rows2) {
-        // 16-row tiles from MMG_DWCONV_TH=16 (A/B knob; default 8)
-        const int th16 = getenv("MMG_DWCONV_TH") ? atoi(getenv("MMG_DWCONV_TH")) == 16 : DW_FWD_TH_DEFAULT == 16;
-        const int TH = th16 ? 16 : 8;
-        const size_t shm2 = (size_t)(TH + 6) * DW_ROWD2 * 4 + 49 * DW_CB * 4;
-        const dim3 grid2(tiles_w * cdiv(H, TH), C / DW_CB, n);
-#define DW_LAUNCH2(FL, T)                                                                                          \
-        do {                                                                                                       \
-            mmg_allow_lds(dwconv7_rows2_kernel<FL, T>, shm2);                                                      \
-            hipLaunchKernelGGL((dwconv7_rows2_kernel<FL, T>), grid2, dim3(256), shm2, stream, (const bf16_t*)x, w, bias, \
-                               (const bf16_t*)add, (bf16_t*)y, H, W, C, tiles_w, nt);                              \
-        } while (0)
-        MMG_NOTE_KERNEL("dwconv7_rows2_kernel<%s, %d>", flip ? "true" : "false", TH);
-        if (flip) { if (th16) DW_LAUNCH2(true, 16); else DW_LAUNCH2(true, 8); }
-        else      { if (th16) DW_LAUNCH2(false, 16); else DW_LAUNCH2(false, 8); }
-#undef DW_LAUNCH2
-        MMG_LAUNCH_CHECK("mmg_dwconv7_nhwc");
-        return 0;
+    if (dw_check(DW_NHWC, DwArgs{n, H, W, C, x && w && y})) return 1;
+    const DwPlan pl = dw_plan(DW_NHWC, n, H, W, C, flip, add != nullptr, 0, dw_knobs());
+    MMG_NOTE_KERNEL("%s", dw_kernel_name(pl.kernel));
+#define FWD_ARGS (const bf16_t*)x, w, bias, (const bf16_t*)add, (bf16_t*)y, H, W, C, pl.tiles_w, pl.nt
+    switch (pl.kernel) {
+#define KV(FLIP) case DK_fwd_##FLIP: DW_LAUNCH(dwconv7_kernel<FLIP>, FWD_ARGS)
+#define KR(FLIP, TH) case DK_rows2_##FLIP##_##TH: DW_LAUNCH((dwconv7_rows2_kernel<FLIP, TH>), FWD_ARGS)
+        DW_FWD_KERNELS(KV, KR)
+#undef KV
+#undef KR
+        default: mmg_set_error("mmg_dwconv7_nhwc: no kernel for plan %d", pl.kernel); return 1;
     }
-    MMG_NOTE_KERNEL("dwconv7_kernel<%s>", flip ? "true" : "false");
-    if (flip) {
-        mmg_allow_lds(dwconv7_kernel<true>, shm);
-        hipLaunchKernelGGL(dwconv7_kernel<true>, grid, dim3(256), shm, stream, (const bf16_t*)x, w, bias, (const bf16_t*)add,
-                           (bf16_t*)y, H, W, C, tiles_w, nt);
-    } else {
-        mmg_allow_lds(dwconv7_kernel<false>, shm);
-        hipLaunchKernelGGL(dwconv7_kernel<false>, grid, dim3(256), shm, stream, (const bf16_t*)x, w, bias, (const bf16_t*)add,
-                           (bf16_t*)y, H, W, C, tiles_w, nt);
-    }
+#undef FWD_ARGS
     MMG_LAUNCH_CHECK("mmg_dwconv7_nhwc");
     return 0;
 }
@@ -496,43 +459,19 @@ MMG_API int mmg_dwconv7_nhwc(const void* x, const float* w, const float* bias, c
 // dw[49][C] += ..., dbias[C] += ...   (fp32, atomics; caller zeroes once per step)
 MMG_API int mmg_dwconv7_wgrad(const void* x, const void* dy, float* dw, float* dbias, int n, int H, int W, int C,
                               hipStream_t stream) {
-    if (dw_check("mmg_dwconv7_wgrad", n, H, W, C)) return 1;
-    MMG_CHECK_ARG(x && dy && dw, "mmg_dwconv7_wgrad: null pointer");
-    const int rows2 = getenv("MMG_DWCONV_ROWS2") ? atoi(getenv("MMG_DWCONV_ROWS2")) : 1;
-    // tile height of the two-rows-per-lane kernel: 16 where the map is tall enough to fill the persistent grid (halo 1.63x), else 8
-    const int th_env = getenv("MMG_DWG_TH") ? atoi(getenv("MMG_DWG_TH")) : 0;
-    const int TH = rows2 ? (th_env == 8 || th_env == 16 ? th_env : ((long)n * cdiv(H, 16) * cdiv(W, DW_TW) * (C / DW_CB) >= 2048 ? 16 : 8)) : DW_TH;
-    const int tiles_w = cdiv(W, DW_TW), tiles_h = cdiv(H, TH);
-    const size_t shm = (size_t)DW_ROWS * DW_ROWD * 4 + 4 * 50 * DW_CB * 4;
-    // ~1024 workgroups in total (4 per CU), each walking its share of the (image, tile) items of one channel slab
-    const int tiles = tiles_w * tiles_h, slabs = C / DW_CB;
-    int per_slab = 1024 / slabs;
-    // a multiple of 8: workgroup x of every slab then lands on XCD x % 8 (ids are x + per_slab * slab), so the slabs of one
-    // pixel - 64-byte pieces of the same 128-byte lines, walked in the same order - share one L2 (measured before: 2.6x the
-    // algorithmic bytes left the L2s)
-    static const int align8 = getenv("MMG_DWG_ALIGN") ? atoi(getenv("MMG_DWG_ALIGN")) : 1;
-    if (align8 && per_slab >= 8) per_slab &= ~7;
-    if (per_slab < 1) per_slab = 1;
-    if (per_slab > n * tiles) per_slab = n * tiles;
-    if (rows2) {
-        const size_t shm2 = (size_t)(TH + 6) * DW_ROWD2 * 4 + 4 * 50 * DW_CB * 4;
-        MMG_NOTE_KERNEL("dwconv7_wgrad_rows2_kernel<%d>", TH);
-        if (TH == 16) {
-            mmg_allow_lds(dwconv7_wgrad_rows2_kernel<16>, shm2);
-            hipLaunchKernelGGL(dwconv7_wgrad_rows2_kernel<16>, dim3(per_slab, slabs), dim3(256), shm2, stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dw, dbias, n, H, W, C, tiles_w, tiles);
-        } else {
-            mmg_allow_lds(dwconv7_wgrad_rows2_kernel<8>, shm2);
-            hipLaunchKernelGGL(dwconv7_wgrad_rows2_kernel<8>, dim3(per_slab, slabs), dim3(256), shm2, stream, (const bf16_t*)x,
-                               (const bf16_t*)dy, dw, dbias, n, H, W, C, tiles_w, tiles);
-        }
-        MMG_LAUNCH_CHECK("mmg_dwconv7_wgrad");
-        return 0;
+    if (dw_check(DW_WGRAD, DwArgs{n, H, W, C, x && dy && dw})) return 1;
+    const DwPlan pl = dw_plan(DW_WGRAD, n, H, W, C, 0, 0, 0, dw_knobs());
+    MMG_NOTE_KERNEL("%s", dw_kernel_name(pl.kernel));
+#define WGRAD_ARGS (const bf16_t*)x, (const bf16_t*)dy, dw, dbias, n, H, W, C, pl.tiles_w, pl.tiles_w * pl.tiles_h
+    switch (pl.kernel) {
+#define KG() case DK_wgrad: DW_LAUNCH(dwconv7_wgrad_kernel, WGRAD_ARGS)
+#define KG2(TH) case DK_wgrad2_##TH: DW_LAUNCH(dwconv7_wgrad_rows2_kernel<TH>, WGRAD_ARGS)
+        DW_WGRAD_KERNELS(KG, KG2)
+#undef KG
+#undef KG2
+        default: mmg_set_error("mmg_dwconv7_wgrad: no kernel for plan %d", pl.kernel); return 1;
     }
-    MMG_NOTE_KERNEL("dwconv7_wgrad_kernel");
-    mmg_allow_lds(dwconv7_wgrad_kernel, shm);
-    hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3(per_slab, slabs), dim3(256), shm, stream, (const bf16_t*)x,
-                       (const bf16_t*)dy, dw, dbias, n, H, W, C, tiles_w, tiles);
+#undef WGRAD_ARGS
     MMG_LAUNCH_CHECK("mmg_dwconv7_wgrad");
     return 0;
 }

@@ -24,35 +24,7 @@
 // while item k is computed (see "Memory pipeline" below).  Pitches (tools: bank model of MI355X_MICROARCH.md, LDS section): plane rows 96 B (b128 reads conflict-free under
 // the real 16-lane grouping; 80 B is 2-way), planes 2128 B apart (b64 writes 2-way), output planes 40-byte rows / 656 B apart
 // (writes conflict-free, transposed reads 2-way), NHWC output pixels 80 B apart (b128 writes conflict-free).
-#include "common.h"
-#include <stdlib.h>
-
-#define DM_T 16                              // output tile edge
-#define DM_H 22                              // halo tile edge
-#define DM_CB 32                             // channels per slab (64 contiguous bytes per pixel)
-#define DM_NPIX (DM_H * DM_H)                // 484
-#define DM_CHUNKS 2048                       // 16-byte chunks a workgroup moves per halo tile (4 per thread; 1936 carry pixels)
-#define DM_IN_BYTES (DM_CHUNKS * 16)         // the NHWC halo tile (the transposed reads of a row's last column group run 2 pixels over: inside)
-#define DM_ROWB 96                           // bytes per plane row (48 bf16: x_in 0..21 data, 22..31 read by the MFMA against zero taps)
-#define DM_PLANE (DM_H * DM_ROWB + 16)       // 2128
-#define DM_PLANAR (DM_CB * DM_PLANE)         // 68 096
-#define DM_OROWB 40                          // a channel's 16 x 16 outputs go back into ITS OWN (consumed) input plane: 40-byte rows
-#define DM_OPIX 80                           // bytes per pixel of the NHWC output tile
-#define DM_OUT_BYTES (DM_T * DM_T * DM_OPIX)
-#define DM_OFF_IN 0
-#define DM_OFF_PLANAR DM_IN_BYTES
-#define DM_OFF_OUT (DM_OFF_PLANAR + DM_PLANAR)
-#define DM_LDS (DM_OFF_OUT + DM_OUT_BYTES)
-// ADD instantiations carry the fp32 accumulators to the output pass WHOLE, as two 16-bit halves through the same 16-bit transposes: the high
-// halves take the path of the bf16 outputs, the low halves go D -> the (consumed) NHWC input tile region, planes DM_LO_PLANE apart (= DM_PLANE
-// mod 256: the bank pattern of the high halves) -> E -> a second NHWC output tile.  F rebuilds the fp32 value, adds the residual operand and
-// rounds ONCE, as the VALU kernels do (rounding conv + bias to bf16 first and the sum again was off by up to half an ulp of the LARGER of the two).
-#define DM_LO_PLANE 848
-#define DM_OFF_OUT_LO (DM_OFF_OUT + DM_OUT_BYTES)
-#define DM_LDS_ADD (DM_OFF_OUT_LO + DM_OUT_BYTES)
-static_assert(DM_LDS_ADD <= 160 * 1024, "LDS budget");
-static_assert(DM_LO_PLANE >= DM_T * DM_OROWB && DM_CB * DM_LO_PLANE <= DM_IN_BYTES && DM_LO_PLANE % 16 == 0, "the low halves fit the input tile region");
-static_assert(DM_PLANE % 16 == 0 && DM_T * DM_OROWB <= DM_PLANE, "alignment / the output rows fit the plane they replace");
+#include "dwconv_plan.h"     // DM_*: the tile and the LDS layout, shared with the host's LDS arithmetic
 
 struct DwM {
     const bf16_t* x; const float* w; const float* bias; const bf16_t* add; bf16_t* y;
@@ -390,38 +362,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void dwconv7_mfma_kernel(const DwM
     }
 }
 
+// validate (dwconv_plan.hip, before any HIP call), plan, launch what the plan names
 MMG_API int mmg_dwconv7_nhwc_mfma(const void* x, const float* w, const float* bias, const void* add, void* y, int n, int H,
                                   int W, int C, int flip, hipStream_t stream) {
-    MMG_CHECK_ARG(x && w && y, "mmg_dwconv7_nhwc_mfma: null pointer");
-    MMG_CHECK_ARG(n > 0 && H > 0 && W > 0 && C > 0 && C % DM_CB == 0, "mmg_dwconv7_nhwc_mfma: n=%d H=%d W=%d C=%d (C must be a multiple of 32)", n, H, W, C);
-    DwM p{(const bf16_t*)x, w, bias, (const bf16_t*)add, (bf16_t*)y, n, H, W, C, cdiv(W, DM_T), cdiv(H, DM_T), 0, 0, 0, 0};
-    p.m_img = (unsigned)((1ULL << 32) / (unsigned long long)(p.tiles_w * p.tiles_h > 1 ? p.tiles_w * p.tiles_h : 2));
-    p.m_tw = (unsigned)((1ULL << 32) / (unsigned long long)(p.tiles_w > 1 ? p.tiles_w : 2));
-    p.nt = (size_t)n * H * W * C * 2 >= ((size_t)256 << 20);
-    p.dbg = DWM_DBG;
-    const long items = (long)n * p.tiles_w * p.tiles_h;
-    const int slabs = C / DM_CB;
-    MMG_CHECK_ARG(items < (1L << 30), "mmg_dwconv7_nhwc_mfma: too many tiles");
-    // one workgroup per CU, a multiple of 8 (XCD groups); never fewer workgroups per XCD group than slabs
-    int cus = mmg_cu_count_cached();
-    int per_xcd = cus / 8;
-    if (per_xcd < slabs) per_xcd = slabs;
-    // small maps: no more streams than items
-    const long want = (items + 7) / 8 * slabs;
-    if (per_xcd > want) per_xcd = (int)(want < slabs ? slabs : want);
-    const int grid = 8 * per_xcd;
-    const int nw = getenv("MMG_DWM_WAVES") ? atoi(getenv("MMG_DWM_WAVES")) : 16;
-    MMG_NOTE_KERNEL("dwconv7_mfma_kernel<%s, %d>", flip ? "true" : "false", nw == 8 ? 8 : 16);
-#define DM_LAUNCH(FL, W_, AD)                                                                                 \
-    do {                                                                                                      \
-        mmg_allow_lds(dwconv7_mfma_kernel<FL, W_, AD>, AD ? DM_LDS_ADD : DM_LDS);                             \
-        hipLaunchKernelGGL((dwconv7_mfma_kernel<FL, W_, AD>), dim3(grid), dim3(W_ * 64), AD ? DM_LDS_ADD : DM_LDS, stream, p);  \
-    } while (0)
-#define DM_LAUNCH_W(FL, AD) do { if (nw == 8) DM_LAUNCH(FL, 8, AD); else DM_LAUNCH(FL, 16, AD); } while (0)
-    if (flip) { if (add) DM_LAUNCH_W(true, true); else DM_LAUNCH_W(true, false); }
-    else      { if (add) DM_LAUNCH_W(false, true); else DM_LAUNCH_W(false, false); }
-#undef DM_LAUNCH_W
-#undef DM_LAUNCH
+    if (dw_check(DW_MFMA, DwArgs{n, H, W, C, x && w && y})) return 1;
+    const DwPlan pl = dw_plan(DW_MFMA, n, H, W, C, flip, add != nullptr, mmg_cu_count_cached(), dw_knobs());
+    const DwM p{(const bf16_t*)x, w, bias, (const bf16_t*)add, (bf16_t*)y, n, H, W, C, pl.tiles_w, pl.tiles_h, pl.nt, pl.m_img, pl.m_tw, DWM_DBG};
+    MMG_NOTE_KERNEL("%s", dw_kernel_name(pl.kernel));
+    switch (pl.kernel) {
+#define KM(FLIP, NW, ADD)                                                                                                   \
+    case DK_mfma_##FLIP##_##NW##_##ADD:                                                                                     \
+        mmg_allow_lds(dwconv7_mfma_kernel<FLIP, NW, ADD>, pl.lds);                                                          \
+        hipLaunchKernelGGL((dwconv7_mfma_kernel<FLIP, NW, ADD>), dim3(pl.gx), dim3(pl.block), pl.lds, stream, p);           \
+        break;
+        DW_MFMA_KERNELS(KM)
+#undef KM
+        default: mmg_set_error("mmg_dwconv7_nhwc_mfma: no kernel for plan %d", pl.kernel); return 1;
+    }
     MMG_LAUNCH_CHECK("mmg_dwconv7_nhwc_mfma");
     return 0;
 }

@@ -3,7 +3,8 @@ kernels of csrc/dwconv7.hip and csrc/dwconv7_mfma.hip.
 
 Imported by tests/test_dwconv_ref_cpu.py (no GPU: the table covers every template instantiation, the exactness preconditions hold on
 the reference alone, the emulation is inside every bar and every mutation of it is caught) and by tests/test_dwconv_gpu.py (the kernels
-against the same reference).  Everything here runs on the CPU in float64.
+against the same reference); tests/test_dwconv_plan_cpu.py holds the host layer's plans (csrc/dwconv_plan.hip) against plan_text, the
+restatement of the launchers' arithmetic below.  Everything here runs on the CPU in float64.
 
 Layout: x, dy, add, y [n, H, W, C]; taps w49 [49, C] tap-major (w49[kh * 7 + kw, c] = weight[c, 0, kh, kw]); bias [C].
     y[n, h, w, c] = bias[c] + sum_{kh, kw} w49[kh * 7 + kw, c] x[n, h + kh - 3, w + kw - 3, c]  (+ add),   zero outside the image
@@ -143,7 +144,7 @@ def mfma_plan(n, H, W, C, cus):
     if per_xcd > want:
         per_xcd = max(want, slabs)
     by_image = n >= 8
-    counts, strides = [], set()
+    counts, strides, slab_items = [], set(), [0] * slabs
     for b in range(8 * per_xcd):
         xcd, j = b & 7, b >> 3
         slab, u = j % slabs, j // slabs
@@ -153,9 +154,10 @@ def mfma_plan(n, H, W, C, cus):
         else:
             seq, first, step = items, u * 8 + xcd, 8 * ns
         counts.append(len(range(first, seq, step)))
+        slab_items[slab] += counts[-1]
         strides.add(step)
     return dict(tiles_w=tiles_w, tiles_h=tiles_h, per_img=per_img, items=items, slabs=slabs, grid=8 * per_xcd, by_image=by_image,
-                min_items=min(counts), max_items=max(counts), strides=strides)
+                min_items=min(counts), max_items=max(counts), strides=strides, slab_items=slab_items)
 
 
 def mfma_halo_paths(H, W):
@@ -165,18 +167,75 @@ def mfma_halo_paths(H, W):
             for y0 in range(0, H, MFMA_T) for x0 in range(0, W, MFMA_T)}
 
 
-def wgrad_plan(case):
-    """mmg_dwconv7_wgrad's grid: per_slab workgroups walk the n * tiles items of a slab with a grid stride."""
+def wgrad_plan(case, align=True):
+    """mmg_dwconv7_wgrad's grid: per_slab workgroups walk the n * tiles items of a slab with a grid stride.  align: MMG_DWG_ALIGN."""
     th, tw = tile_hw(case)
     tiles, slabs = cdiv(case.W, tw) * cdiv(case.H, th), case.C // CB
     per_slab = 1024 // slabs
-    if per_slab >= 8:
+    if align and per_slab >= 8:
         per_slab &= ~7
     per_slab = max(per_slab, 1)
     capped = per_slab > case.n * tiles
     per_slab = min(per_slab, case.n * tiles)
     return dict(TH=th, tiles=tiles, items=case.n * tiles, per_slab=per_slab, capped=capped, min_items=case.n * tiles // per_slab,
                 max_items=cdiv(case.n * tiles, per_slab))
+
+
+# Dynamic LDS, from the launchers before the host layer csrc/dwconv_plan.hip.  VALU kernels: the staged halo tile, rows of 38 columns x 16
+# channel pairs (dwords) padded by 16 dwords in the one-row kernels ([8 + 6] rows) and by 8 in the two-row kernels ([TH + 6] rows); behind
+# it the slab's taps [49][32] fp32 (forward) or the reduction buffer [4 waves][50][32] fp32 (weight gradient).  Matrix cores: the NHWC halo
+# tile (2048 chunks of 16 bytes), 32 channel planes of 22 rows x 96 bytes + 16, the NHWC output tile (16 x 16 pixels x 80 bytes) - and a
+# second output tile for the low halves of the accumulators when `add` is given.
+ROWD, ROWD2 = 38 * 16 + 16, 38 * 16 + 8
+MFMA_LDS = 2048 * 16 + 32 * (22 * 96 + 16) + 16 * 16 * 80
+MFMA_LDS_ADD = MFMA_LDS + 16 * 16 * 80
+NT_BYTES = 256 << 20              # outputs of this many bytes and more are stored past L2
+
+
+def lds(case):
+    """Dynamic LDS bytes of the case's launch."""
+    if case.op == "conv" and case.mfma:
+        return MFMA_LDS_ADD if case.add else MFMA_LDS
+    th, _ = tile_hw(case)
+    tile = (14 * ROWD if case.rows2 == 0 else (th + 6) * ROWD2) * 4
+    return tile + (49 * CB * 4 if case.op == "conv" else 4 * 50 * CB * 4)
+
+
+def block(case):
+    """Threads per workgroup: the VALU kernels 256, the matrix-core kernel 64 per wave."""
+    return 64 * (8 if case.waves == 8 else 16) if case.op == "conv" and case.mfma else 256
+
+
+def nt(case):
+    """Streaming stores: an output of 256 MiB and more (the weight gradient has no such output)."""
+    return int(case.op == "conv" and case.n * case.H * case.W * case.C * 2 >= NT_BYTES)
+
+
+def grid(case, cus, align=True):
+    """(x, y, z) of the case's launch on a device of `cus` CUs (only the matrix-core kernel reads them)."""
+    th, tw = tile_hw(case)
+    if case.op == "wgrad":
+        return wgrad_plan(case, align)["per_slab"], case.C // CB, 1
+    if case.mfma:
+        return mfma_plan(case.n, case.H, case.W, case.C, cus)["grid"], 1, 1
+    return cdiv(case.W, tw) * cdiv(case.H, th), case.C // CB, case.n
+
+
+def plan_args(case, cus):
+    """The arguments of mmg_dwconv7_plan for the case."""
+    op = 2 if case.op == "wgrad" else (1 if case.mfma else 0)
+    return op, case.n, case.H, case.W, case.C, int(case.flip and op != 2), int(case.add and op != 2), cus
+
+
+def plan_text(case, cus, align=True):
+    """What mmg_dwconv7_plan returns for the case on a device of `cus` CUs."""
+    th, tw = tile_hw(case)
+    x, y, z = grid(case, cus, align)
+    text = (f"{kernel_note(case)} grid=({x},{y},{z}) block={block(case)} lds={lds(case)} nt={nt(case)} tile={th}x{tw} "
+            f"items={case.n * cdiv(case.H, th) * cdiv(case.W, tw)}")
+    if case.op == "conv" and case.mfma:
+        text += f" add={int(case.add)} by_image={int(case.n >= 8)}"
+    return text
 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------------

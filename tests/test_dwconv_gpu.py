@@ -136,6 +136,9 @@ def test_kernels_against_float64(case, dev, monkeypatch):
         bad += [f"{k}: worst ratio {v} > 1" for k, v in res.items() if not v <= 1.0]
     if name != R.kernel_note(case):
         bad.append(f"launched {name!r}, the table says {R.kernel_note(case)!r}")
+    planned = _hip.load().mmg_dwconv7_plan(*R.plan_args(case, 0)).decode().split(" grid=")[0]      # cus = 0: this device's
+    if planned != name:
+        bad.append(f"launched {name!r}, mmg_dwconv7_plan names {planned!r}")
     assert not bad, bad
 
 
